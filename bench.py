@@ -16,14 +16,28 @@ layers, D=64, K=8, H=100).  Sample sharding, replicated weights:
                    BASELINE config c4 (8M rows over 8 GPUs);
   --scaling strong the --global-batch rows (2^20) are split over the ranks
                    (dist.shard_range): the north star's strong-scaling target;
-  --scaling both   (default at N > 1) both loops in one invocation: weak is
+  --scaling both   (default at N > 1 with --full) both loops in one invocation: weak is
                    the line's value, strong is its "strong" sub-object.
 With N > 1 each step ends with the NLL all-reduce of [sum log p, count]
 (RCCL; --backend gloo runs the same path over gloo, e.g. N ranks on one
 device in a test).  Status checks run deferred (config.STRICT_CHECKS =
 "deferred": no host sync per step; flushed, and raised, after the timed loop).
 
-Rank 0 prints ONE JSON line with:
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON
+line: value, ms_per_step (milliseconds per timed step) and the configuration.
+At N > 1 it times the weak loop only unless --scaling says otherwise.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller,
+the log_prob of every row of this rank, as float32 DIR/log_prob.npy (N > 1:
+DIR/log_prob_rank<r>.npy per rank, and the all-reduced NLL as DIR/nll.npy; a
+second loop's arrays carry its mode as a prefix, strong_).  The inputs and
+weights are seeded, so two builds run with the same arguments can be compared
+output for output.  An array that would take the dump past DUMP_BUDGET_BYTES
+in all is written as a fixed, seeded sample of its rows (DIR/<name>_rows.npy
+holds the row numbers as float64).
+
+``--full`` adds everything else the benchmark measures and checks; the line
+then also holds:
   roofline      the dominant kernel's time from HIP events recorded live on
                 its launch stream, against a hardware roofline: the dense
                 f16 MFMA peak for the fused kernels (frac = the MFMA floor of
@@ -38,6 +52,9 @@ Rank 0 prints ONE JSON line with:
                 (outside the timed region)
   cpu_baseline  the CPU oracle (torch-CPU fp32 restatement of the reference
                 path) on a bounded sample of the same workload, best of 3
+  kernels       per-kernel launch counts and mean times (the event timer)
+and at N > 1 the default --scaling is "both".  --no-cpu-baseline, --no-timer
+and --parity-rows 0 switch single parts of a --full run off.
 """
 from __future__ import annotations
 
@@ -624,6 +641,29 @@ def load_traffic(kernel, workload, batch=None):
     return int(rec["bytes_per_launch"] * scale)
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files of one invocation together
+
+
+def dump_array(dirname, name, t, budget):
+    """Write tensor t (rows first) as dirname/name.npy: float32, or float64 for
+    a double tensor.  When it would take more than budget bytes, a sorted
+    sample of its rows drawn without replacement by a generator seeded 0 (the
+    same rows in every run of the same shape) is written instead, with the row
+    numbers in dirname/name_rows.npy."""
+    import numpy as np
+    a = t.detach().cpu().numpy()
+    a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    a = a.reshape(1) if a.ndim == 0 else a
+    os.makedirs(dirname, exist_ok=True)
+    row = max(1, int(np.prod(a.shape[1:]))) * a.itemsize + 8  # + its row number
+    if a.shape[0] * row > budget:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, int(budget // row)),
+                                                       replace=False))
+        np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(n):
     """``--gpus N`` (N > 1) started without a launcher (no WORLD_SIZE in the
     environment): start the N rank processes of this same command line, one
@@ -665,17 +705,23 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default=None, choices=("weak", "strong", "both"),
                     help="weak: --batch rows per GPU; strong: --global-batch rows split over the GPUs; "
-                         "both (the default for N > 1): weak is the line's value, strong its 'strong' object")
+                         "both (the default for N > 1 with --full): weak is the line's value, strong its "
+                         "'strong' object")
     ap.add_argument("--batch", type=int, default=None,
                     help="samples per GPU (weak scaling; default 2^20, c1 4096)")
     ap.add_argument("--global-batch", type=int, default=None,
                     help="samples in all (strong scaling; default 2^20, c1 4096)")
     ap.add_argument("--backend", default=None, choices=("nccl", "gloo"),
                     help="torch.distributed backend for N > 1 (default: nccl = RCCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel event timer and roofline, the parity check against the CPU "
+                         "oracle, the CPU baseline and, at N > 1, the strong-scaling loop")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the log_prob the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--parity-rows", type=int, default=None,
-                    help="rows checked against the CPU oracle after the timed loop (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-timer", action="store_true", help="skip the per-kernel event timer")
+                    help="--full: rows checked against the CPU oracle after the timed loop (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-timer", action="store_true", help="--full without the per-kernel event timer")
     ap.add_argument("--no-status-checks", action="store_true",
                     help="diagnostic builds only (ablations whose results are not valid): no status checks")
     ap.add_argument("--unfused", action="store_true", help="disable the fused MFMA layer kernel")
@@ -689,6 +735,8 @@ def main():
     ap.add_argument("--dist", action="store_true",
                     help="a process group and the NLL all-reduce even at N = 1 (RCCL on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     dflt = DEFAULT_BATCH.get(args.workload, 1 << 20)
@@ -712,10 +760,13 @@ def main():
     config.STRICT_CHECKS = True if args.sync_checks else "deferred"
     if args.no_status_checks:
         config.STRICT_CHECKS = False
-    # N > 1 times both modes by default: weak (the line's value, c4) and strong
-    # (the metric's 1M x 64 split over the ranks, in the line's "strong" object)
-    scaling = args.scaling or ("both" if world > 1 else "weak")
+    # N > 1 with --full times both modes by default: weak (the line's value, c4) and
+    # strong (the metric's 1M x 64 split over the ranks, in the line's "strong" object)
+    scaling = args.scaling or ("both" if world > 1 and args.full else "weak")
     modes = ["weak", "strong"] if scaling == "both" else [scaling]
+    use_timer = args.full and not args.no_timer
+    # --dump-outputs: every rank's log_prob per mode, in equal shares of the budget
+    dump_budget = DUMP_BUDGET_BYTES // (world * len(modes)) - 4096
 
     model, sd, _ = build_model(args.workload, device)
     def graph_for(B):
@@ -765,7 +816,7 @@ def main():
         flush_status_checks()
         progress("%s: timed loop" % mode)
         timer = None
-        if not args.no_timer:
+        if use_timer:
             timer = kernels.TIMER = kernels.KernelTimer()
             if graphed is not None:
                 # a replay launches nothing from the host to time: the per-kernel
@@ -793,15 +844,26 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         progress("%s: %.4f ms per step" % (mode, dt / args.steps * 1e3))
+        if args.dump_outputs:
+            # the last timed step's return value (a graph replay's output buffer: nothing
+            # has replayed since), before anything else of this run touches the device
+            pre = "" if mode == modes[0] else mode + "_"
+            dump_array(args.dump_outputs, pre + ("log_prob" if world == 1 else "log_prob_rank%d" % rank),
+                       lp, dump_budget)
+            if rank == 0 and res["nll"] is not None:
+                dump_array(args.dump_outputs, pre + "nll", res["nll"], 4096)
+            progress("%s: outputs written to %s" % (mode, args.dump_outputs))
         res.update(mode=mode, B=B, total=total, x=x, lp=lp, dt=dt, graphed=graphed is not None,
                    summary=timer.summary() if timer is not None else {})
         return res
 
     results = [run(m) for m in modes]
     if rank == 0:
-        sd_cpu = {k: v.cpu() for k, v in sd.items()}
+        sd_cpu = {k: v.cpu() for k, v in sd.items()} if args.full else None
         n_par = args.parity_rows if args.parity_rows is not None else \
             (4096 if args.workload == "c5" else 16384)
+        if not args.full:
+            n_par = 0
 
         def record(r):
             value = r["total"] * args.steps / r["dt"]
@@ -819,7 +881,7 @@ def main():
         main_r = results[0]
         value, rl, par = record(main_r)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure
             cpu = cpu_baseline(args.workload, sd_cpu)
         desc = WORKLOADS[args.workload][0]
         out = {
@@ -831,6 +893,7 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(main_r["dt"] / args.steps * 1e3, 4),
             "higher_is_better": True,
+            "full": bool(args.full),
             "scaling": main_r["mode"],
             "vs_baseline": (round(value / BASELINE_CPU[args.workload], 3)
                             if args.workload in BASELINE_CPU else None),

@@ -32,3 +32,27 @@ def test_make_x_per_workload():
     assert bench.make_x("c3", 64, g, "cpu").shape == (64, 64)
     assert bench.make_x("c5", 8, g, "cpu").shape == (8, 256)
     assert bench.DEFAULT_BATCH.get("c1") == 4096
+
+
+def test_dump_array_whole_and_sampled(tmp_path):
+    """--dump-outputs files: float32 (float64 for a double tensor); an array
+    within the budget is written whole, a larger one as the same seeded,
+    sorted row sample in every run, with its row numbers beside it."""
+    import numpy as np
+    d = str(tmp_path / "out")
+    lp = torch.arange(1000, dtype=torch.float32) * 0.5
+    bench.dump_array(d, "log_prob", lp, 1 << 20)
+    a = np.load(os.path.join(d, "log_prob.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, lp.numpy())
+    assert not os.path.exists(os.path.join(d, "log_prob_rows.npy"))
+    bench.dump_array(d, "nll", torch.tensor(1.25, dtype=torch.float64), 4096)
+    n = np.load(os.path.join(d, "nll.npy"))
+    assert n.dtype == np.float64 and n.shape == (1,) and n[0] == 1.25
+    for name in ("s1", "s2"):
+        bench.dump_array(d, name, lp, 1200)
+    s1, r1 = np.load(os.path.join(d, "s1.npy")), np.load(os.path.join(d, "s1_rows.npy"))
+    s2, r2 = np.load(os.path.join(d, "s2.npy")), np.load(os.path.join(d, "s2_rows.npy"))
+    assert np.array_equal(s1, s2) and np.array_equal(r1, r2)
+    assert s1.nbytes + r1.nbytes <= 1200 and len(s1) == 100
+    assert np.all(np.diff(r1) > 0) and np.array_equal(s1, lp.numpy()[r1.astype(np.int64)])
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000

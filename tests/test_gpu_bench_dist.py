@@ -45,7 +45,7 @@ def _bench_world2(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--parity-rows", "1024", *extra]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--parity-rows", "1024", *extra]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -99,7 +99,7 @@ def test_bench_gpus2_without_launcher_spawns_ranks(hip_device):
     rows = 12288
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--scaling", "weak", "--batch", str(rows), "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--parity-rows", "1024"]
+           "--full", "--no-cpu-baseline", "--parity-rows", "1024"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300, env=env)
@@ -126,7 +126,7 @@ def test_bench_rccl_world1_nll_vs_oracle(hip_device):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "1", "--backend", "nccl", "--dist",
-           "--batch", str(rows), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--batch", str(rows), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--parity-rows", "1024"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300, env=env)
@@ -149,7 +149,7 @@ def test_bench_c1_moons_vs_oracle(hip_device):
     """BASELINE c1 (2-D two moons, 4-layer RealNVP, H=100, B=4096) through
     bench.py on the GPU: the benched log_prob of every row vs the oracle."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c1", "--steps", "5",
-           "--warmup", "2", "--no-cpu-baseline", "--parity-rows", "4096"]
+           "--warmup", "2", "--full", "--no-cpu-baseline", "--parity-rows", "4096"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

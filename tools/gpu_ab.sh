@@ -16,7 +16,7 @@ fi
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs timeout -k 10 200 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"; rc=$?
+  env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"; rc=$?
   echo "[$envs] rc=$rc"; python -c "import json;d=json.load(open('$OUT/bench_$i.json'));print(d['value']/1e6,'M/s',d['roofline']['mean_ms'],'ms',d['kernels'])" 2>/dev/null || tail -3 "$OUT/bench_$i.err"
   [ $rc -ne 0 ] && exit $rc
 done

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; cd "$ROOT"
 for r in $(seq 1 "$ROUNDS"); do
   for v in "$@"; do
     n=${v%%=*}; lib=${v#*=}
-    NFK_LIBRARY=$ROOT/$lib timeout -k 10 200 python bench.py --no-cpu-baseline --parity-rows 2048 ${BENCH_ARGS:-} \
+    NFK_LIBRARY=$ROOT/$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --parity-rows 2048 ${BENCH_ARGS:-} \
         > "$OUT/${n}_$r.json" 2> "$OUT/${n}_$r.err"; rc=$?
     [ $rc -ne 0 ] && { echo "$n round $r rc=$rc"; tail -5 "$OUT/${n}_$r.err"; exit $rc; }
   done

@@ -22,20 +22,20 @@ if [ $TESTS = 1 ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; rc=$?
   echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"; [ $rc = 0 ] || exit $rc
 fi
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
 echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"; [ $rc = 0 ] || exit $rc
 i=0
 IFS=';' read -ra SETS <<< "$EXTRA"
 for a in "${SETS[@]}"; do
   [ -z "${a// }" ] && continue
   i=$((i+1))
-  timeout -k 10 300 python bench.py --no-cpu-baseline $a > "$OUT/bench_x$i.json" 2> "$OUT/bench_x$i.err"; rc=$?
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline $a > "$OUT/bench_x$i.json" 2> "$OUT/bench_x$i.err"; rc=$?
   echo "bench_x$i ($a) rc=$rc"; cat "$OUT/bench_x$i.json"; [ $rc = 0 ] || { tail -3 "$OUT/bench_x$i.err"; exit $rc; }
 done
 export TMPDIR=/tmp
 if [ $PROF = 1 ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o trace \
-      -- python3 "$ROOT/bench.py" --no-cpu-baseline --parity-rows 0 > "$OUT/prof.log" 2>&1; rc=$?
+      -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --parity-rows 0 > "$OUT/prof.log" 2>&1; rc=$?
   grep '^{' "$OUT/prof.log" > "$OUT/prof_bench.json" || true
   echo "rocprof rc=$rc"; [ $rc = 0 ] || { tail -3 "$OUT/prof.log"; exit $rc; }
 fi
