@@ -25,13 +25,11 @@
 #include <cstdio>
 
 #include "../../include/nfk.h"
+#include "nfk_mfma.h"
 
 int nfk_set_error(const char* msg);
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDhWaves = 8;
 constexpr int kDhMaxNT = 8;  // H <= 128
@@ -45,10 +43,6 @@ int launch_status(const char* what) {
         return (int)e;
     }
     return 0;
-}
-
-__device__ __forceinline__ f32x4 mfma16(h8 a, h8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
 // pack: [0] = 1 / weight scale, then from half offset 128 the fragments

@@ -22,7 +22,7 @@
 // fp32 needs 8 x 32 -- and on gfx950 fp32 MFMA and VALU share one issue port
 // (tools/ubench_coexec.hip), so MFMA cycles are paid in full.
 //
-// Hidden features are permuted (hid_feature in nfk_fused_impl.h) so that the
+// Hidden features are permuted (hid_feature in nfk_pack.h) so that the
 // accumulators of one layer ARE the B fragments of the next: no LDS round trip.
 // Output layer: per chunk of 16 coordinates the 3K-1 parameter tiles are
 // produced in three phases (W logits, H logits, D logits; H first when
@@ -67,113 +67,46 @@ struct PackArgs {
     Layout L;
 };
 
-// max |W| of layers 1, 2, 3 into hdr[0..2] as uint bits (non-negative floats
-// order like their bit patterns)
+// max |W| of layers 1, 2, 3 into the header
 __global__ __launch_bounds__(256) void k_pack_max(PackArgs a) {
     const Layout& L = a.L;
-    const int64_t n1 = (int64_t)L.H * L.n_lo, n2 = (int64_t)L.H * L.H, n3 = (int64_t)L.n_up * L.P * L.H;
-    float m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n1 + n2 + n3;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        if (g < n1)
-            m1 = fmaxf(m1, fabsf(a.w0[g]));
-        else if (g < n1 + n2)
-            m2 = fmaxf(m2, fabsf(a.w2[g - n1]));
-        else
-            m3 = fmaxf(m3, fabsf(a.w4[g - n1 - n2]));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        m1 = fmaxf(m1, __shfl_xor(m1, off, 64));
-        m2 = fmaxf(m2, __shfl_xor(m2, off, 64));
-        m3 = fmaxf(m3, __shfl_xor(m3, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        unsigned int* h = reinterpret_cast<unsigned int*>(a.out);
-        atomicMax(h, __float_as_uint(m1));
-        atomicMax(h + 1, __float_as_uint(m2));
-        atomicMax(h + 2, __float_as_uint(m3));
-    }
+    nfk_absmax3(a.w0, (int64_t)L.H * L.n_lo, a.w2, (int64_t)L.H * L.H, a.w4, (int64_t)L.n_up * L.P * L.H, a.out);
 }
 
-// power-of-two exponent s with max|W| 2^s in [2^14, 2^15)
-__device__ int scale_exp(float maxw) {
-    if (!(maxw > 0.0f) || !(maxw < 3.0e38f)) return 0;
-    int e;
-    frexpf(maxw, &e);  // maxw = m 2^e, m in [0.5, 1)
-    return 15 - e;
-}
-
-__device__ uint32_t f16_part_pair(float v0, float v1, int part) {
-    const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-    const _Float16 r0 = part ? (_Float16)(v0 - (float)h0) : h0;
-    const _Float16 r1 = part ? (_Float16)(v1 - (float)h1) : h1;
-    return (uint32_t)__builtin_bit_cast(uint16_t, r0) | ((uint32_t)__builtin_bit_cast(uint16_t, r1) << 16);
-}
-
-// word of an f16-split record (f16 blocks, tail blocks, bias block) with
-// nt tiles; row(t, i) and the weight row pointer come from the caller's lambda
-template <class RowF, class BiasF>
-__device__ uint32_t pack_record_word(int blk, int wl, const Layout& L, int nt, float sc, float bsc,
-                                     RowF row_of, BiasF bias_of) {
-    const int nf = L.KBH * nt * 2, ntg = L.T1 ? (nt + 1) / 2 : 0;
-    if (blk < nf) {
-        const int part = blk & 1, idx = blk >> 1, kb = idx / nt, t = idx - kb * nt;
-        const int lane = wl >> 2, j = 2 * (wl & 3);
-        const int k0 = 32 * kb + 8 * (lane >> 4) + j;
-        const float* w = row_of(t, lane & 15);
-        float v0 = 0.0f, v1 = 0.0f;
-        if (w != nullptr) {
-            const int klim = L.T1 ? 32 * L.KBH : L.H;  // the tail step owns k >= 32 KBH
-            if (k0 < klim && k0 < L.H) v0 = w[k0] * sc;
-            if (k0 + 1 < klim && k0 + 1 < L.H) v1 = w[k0 + 1] * sc;
-        }
-        return f16_part_pair(v0, v1, part);
+// rows of one W / H / D record of the output layer: row i of tile t = parameter
+// pbase + param(t, i) (np of them) of coordinate coord(i) (Layout: wide form or
+// 16-coordinate form)
+struct ChunkRows {
+    const PackArgs& a;
+    int chunk, pbase, np;
+    __device__ int64_t row(int t, int i) const {  // row of w4 / b4, -1: padding
+        const Layout& L = a.L;
+        const int jc = L.wide ? 8 * chunk + 2 * (i >> 2) + ((i >> 1) & 1) : 16 * chunk + i;
+        const int p = L.wide ? 2 * t + (i & 1) : t;
+        return (jc < L.n_up && p < np) ? (int64_t)jc * L.P + pbase + p : -1;
     }
-    if (blk < nf + ntg) return tail_word(blk - nf, wl, nt, 32 * L.KBH, L.H, sc, row_of);
-    const int t = wl >> 4, i = wl & 15;  // bias block [tile][row]
-    return __float_as_uint(t < nt ? bias_of(t, i) * bsc : 0.0f);
-}
-
-struct PackScales {
-    float sc1, sc2, sc3, bs2, bs3;
+    __device__ float val(int t, int i, int k) const {
+        const int64_t r = row(t, i);
+        return (r >= 0 && k < a.L.H) ? a.w4[r * a.L.H + k] : 0.0f;
+    }
+    __device__ float bias(int t, int i) const {
+        const int64_t r = row(t, i);
+        return r >= 0 ? a.b4[r] : 0.0f;
+    }
 };
 
-// Word g (>= L.o_h1) of the record layout (nfk_fused_impl.h).
+// Word g (>= L.o_h1) of the record layout (nfk_pack.h): whole records.
 __device__ uint32_t pack_word(const PackArgs& a, int64_t g, const PackScales& ps) {
     const Layout& L = a.L;
-    const float sc1 = ps.sc1, sc2 = ps.sc2, sc3 = ps.sc3, bs2 = ps.bs2, bs3 = ps.bs3;
-    const int kbh = L.KBH;
     if (g < L.o_h2) {  // layer 1: KB1 f16 k-blocks over the n_lo inputs + unscaled bias
         const int64_t w = g - L.o_h1;
-        const int blk = (int)(w >> 8), wl = (int)(w & 255);
-        if (blk < L.KB1 * L.HT * 2) {
-            const int part = blk & 1, idx = blk >> 1, kb = idx / L.HT, t = idx - kb * L.HT;
-            const int lane = wl >> 2, j = 2 * (wl & 3);
-            const int f = hid_feature(t, lane & 15, kbh), k0 = 32 * kb + 8 * (lane >> 4) + j;
-            float v0 = 0.0f, v1 = 0.0f;
-            if (f < L.H) {
-                if (k0 < L.n_lo) v0 = a.w0[(int64_t)f * L.n_lo + k0] * sc1;
-                if (k0 + 1 < L.n_lo) v1 = a.w0[(int64_t)f * L.n_lo + k0 + 1] * sc1;
-            }
-            return f16_part_pair(v0, v1, part);
-        } else {
-            const int t = wl >> 4, f = hid_feature(t, wl & 15, kbh);
-            return __float_as_uint((t < L.HT && f < L.H) ? a.b0[f] : 0.0f);
-        }
+        return record_word(L.HT, (int)(w >> 8), (int)(w & 255), L.KB1, 0, L.HT, 0, ps.sc1, ps.bs1,
+                           HidRows<ColPlain>{a.w0, a.b0, L.H, L.n_lo, L.KBH, L.T1, ColPlain{L.n_lo}});
     }
     if (g < L.o_w3) {  // layer 2
         const int64_t w = g - L.o_h2;
-        return pack_record_word(
-            (int)(w >> 8), (int)(w & 255), L, L.HT, sc2, bs2,
-            [&](int t, int i) -> const float* {
-                const int f = hid_feature(t, i, kbh);
-                return f < L.H ? a.w2 + (int64_t)f * L.H : nullptr;
-            },
-            [&](int t, int i) -> float {
-                const int f = hid_feature(t, i, kbh);
-                return f < L.H ? a.b2[f] : 0.0f;
-            });
+        return record_word(L.HT, (int)(w >> 8), (int)(w & 255), L.KBH, L.T1, L.HT, 0, ps.sc2, ps.bs2,
+                           hid_rows(a.w2, a.b2, L.H, L.KBH, L.T1));
     }
     // output layer: chunk, phase (W, H, D)
     const int64_t w3 = g - L.o_w3;
@@ -191,36 +124,18 @@ __device__ uint32_t pack_word(const PackArgs& a, int64_t g, const PackScales& ps
             np = L.K - 1;
         }
     }
-    // (coordinate, parameter) of row i of tile t (Layout: wide form or 16-coordinate form)
-    auto coord = [&](int i) { return L.wide ? 8 * chunk + 2 * (i >> 2) + ((i >> 1) & 1) : 16 * chunk + i; };
-    auto param = [&](int t, int i) { return L.wide ? 2 * t + (i & 1) : t; };
-    return pack_record_word(
-        b, (int)(w3 & 255), L, nt, sc3, bs3,
-        [&](int t, int i) -> const float* {
-            const int jc = coord(i), p = param(t, i);
-            return (jc < L.n_up && p < np) ? a.w4 + ((int64_t)jc * L.P + pbase + p) * L.H : nullptr;
-        },
-        [&](int t, int i) -> float {
-            const int jc = coord(i), p = param(t, i);
-            return (jc < L.n_up && p < np) ? a.b4[(int64_t)jc * L.P + pbase + p] : 0.0f;
-        });
+    return record_word(nt, b, (int)(w3 & 255), L.KBH, L.T1, nt, 0, ps.sc3, ps.bs3, ChunkRows{a, chunk, pbase, np});
 }
 
-// header words: the unscale factors (words 0-2 hold the maxima), and the scales
+// the scales of this pack; thread g < 256 also writes header word g (the NSF
+// form: layer-1 bias unscaled)
 __device__ PackScales pack_header(const PackArgs& a, int64_t g) {
-    const unsigned int* hdr = reinterpret_cast<const unsigned int*>(a.out);
-    const int s1 = scale_exp(__uint_as_float(hdr[0])), s2 = scale_exp(__uint_as_float(hdr[1])),
-              s3 = scale_exp(__uint_as_float(hdr[2]));
-    uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
-    if (g == 3) out[g] = __float_as_uint(ldexpf(1.0f, -s1));
-    if (g == 4) out[g] = __float_as_uint(ldexpf(1.0f, -(s2 + 14)));
-    if (g == 5) out[g] = __float_as_uint(ldexpf(1.0f, -(s3 + 14)));
-    if (g >= 6 && g < 256) out[g] = 0;
-    return PackScales{ldexpf(1.0f, s1), ldexpf(1.0f, s2), ldexpf(1.0f, s3), ldexpf(1.0f, s2 + 14),
-                      ldexpf(1.0f, s3 + 14)};
+    const PackScales ps = pack_scales(a.out, true);
+    if (g < kHdrWords) write_header_word(reinterpret_cast<uint32_t*>(a.out), (int)g, ps, true);
+    return ps;
 }
 
-// One thread per packed 32-bit word (layout described in nfk_fused_impl.h).
+// One thread per packed 32-bit word (layout described in nfk_pack.h).
 __global__ __launch_bounds__(256) void k_pack(PackArgs a) {
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < a.L.total;

@@ -183,164 +183,36 @@ struct ArPackArgs {
 __global__ __launch_bounds__(256) void k_ar_max(ArPackArgs a) {
     const int i = 1 + (int)blockIdx.y;  // conditioner
     const float* const* w = a.w + (int64_t)(i - 1) * 6;
-    const int64_t n1 = (int64_t)a.H * 2 * i, n2 = (int64_t)a.H * a.H, n3 = (int64_t)a.d.P * a.H;
-    float m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n1 + n2 + n3;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        if (g < n1)
-            m1 = fmaxf(m1, fabsf(w[0][g]));
-        else if (g < n1 + n2)
-            m2 = fmaxf(m2, fabsf(w[2][g - n1]));
-        else
-            m3 = fmaxf(m3, fabsf(w[4][g - n1 - n2]));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        m1 = fmaxf(m1, __shfl_xor(m1, off, 64));
-        m2 = fmaxf(m2, __shfl_xor(m2, off, 64));
-        m3 = fmaxf(m3, __shfl_xor(m3, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        unsigned int* h = reinterpret_cast<unsigned int*>(a.out);
-        atomicMax(h, __float_as_uint(m1));
-        atomicMax(h + 1, __float_as_uint(m2));
-        atomicMax(h + 2, __float_as_uint(m3));
-    }
-}
-
-__device__ int ar_scale_exp(float maxw) {  // 2^s max|W| in [2^14, 2^15)
-    if (!(maxw > 0.0f) || !(maxw < 3.0e38f)) return 0;
-    int e;
-    frexpf(maxw, &e);
-    return 15 - e;
-}
-
-// Word wl of block blk of a sub-record holding tiles [T0, T0 + NS) of an
-// nt-tile record over a kbn-k-block contraction (val(t, row, k): the
-// unscaled weight of row `row` of tile t at contraction index k, 0 outside),
-// then (t1) its tail block over contraction indices 32 kbn + 0..3 and the
-// record's bias block [tile][row].  Block order and word layout are those
-// gemm_h reads (nfk_fused_impl.h: k-block fragments, tail_word, bias).
-template <class ValF, class BiasF>
-__device__ uint32_t ar_sub_word(int ns, int blk, int wl, int kbn, int t1, int nt, int T0, float sc, float bsc,
-                                ValF val, BiasF bias) {
-    const int nf = kbn * ns * 2, ntg = t1 == 1 ? (ns + 1) / 2 : 0;
-    if (t1 == 2 && blk >= nf) {
-        // 16-feature tail: the bias block first, then per tile {A1, A2}: lane l
-        // (row l & 15, lane group g = l >> 4) element j of A1 = lo (j < 4) / hi
-        // (j >= 4) weight of feature 32 kbn + 4 g + (j & 3), of A2 = hi (j < 4) / 0;
-        // against B1 = {hi, lo} and B2 = {hi, 0} of the half tile's 4 rows
-        if (blk == nf) {  // the sub-record's own tiles (gemm_h BREL)
-            const int tt = wl >> 4, t = T0 + tt, r = wl & 15;
-            return __float_as_uint(tt < ns && t < nt ? bias(t, r) * bsc : 0.0f);
-        }
-        const int tt = blk - nf - 1;
-        if (tt >= 2 * ns) return 0u;
-        const int t = T0 + (tt >> 1), which = tt & 1;
-        if (t >= nt) return 0u;
-        const int lane = wl >> 2, g = lane >> 4, row = lane & 15, jp = 2 * (wl & 3);
-        _Float16 hv[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int j = jp + e;
-            const float w = val(t, row, 32 * kbn + 4 * g + (j & 3)) * sc;
-            const _Float16 wh = (_Float16)w;
-            if (which == 0)
-                hv[e] = j < 4 ? (_Float16)(w - (float)wh) : wh;
-            else
-                hv[e] = j < 4 ? wh : (_Float16)0.0f;
-        }
-        return (uint32_t)__builtin_bit_cast(uint16_t, hv[0]) | ((uint32_t)__builtin_bit_cast(uint16_t, hv[1]) << 16);
-    }
-    if (blk < nf) {
-        const int part = blk & 1, idx = blk >> 1, kb = idx / ns, t = T0 + (idx - kb * ns);
-        if (t >= nt) return 0u;
-        const int lane = wl >> 2, j = 2 * (wl & 3), k0 = 32 * kb + 8 * (lane >> 4) + j;
-        return nfk_f16_part_pair(val(t, lane & 15, k0) * sc, val(t, lane & 15, k0 + 1) * sc, part);
-    }
-    if (blk < nf + ntg) {  // tail: (hi, hi, lo, 0) of the sub-record's tile pair (tail_word's layout)
-        const int t = T0 + 2 * (blk - nf) + ((wl & 3) >> 1), lane = wl >> 2, j = 2 * (wl & 1), qq = lane >> 4;
-        if (t >= nt || qq == 3) return 0u;
-        const int kb0 = 32 * kbn;
-        return nfk_f16_part_pair(val(t, lane & 15, kb0 + j) * sc, val(t, lane & 15, kb0 + j + 1) * sc,
-                                 qq == 2 ? 1 : 0);
-    }
-    if (blk == nf + ntg) {  // the sub-record's own tiles (gemm_h BREL): records of > 16 tiles
-        const int tt = wl >> 4, t = T0 + tt, r = wl & 15;
-        return __float_as_uint(tt < ns && t < nt ? bias(t, r) * bsc : 0.0f);
-    }
-    return 0u;  // padding to SB blocks
+    nfk_absmax3(w[0], (int64_t)a.H * 2 * i, w[2], (int64_t)a.H * a.H, w[4], (int64_t)a.d.P * a.H, a.out);
 }
 
 __global__ __launch_bounds__(256) void k_ar_pack(ArPackArgs a) {
     const ArDims& d = a.d;
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
-    const unsigned int* hdr = reinterpret_cast<const unsigned int*>(a.out);
-    const int s1 = ar_scale_exp(__uint_as_float(hdr[0])), s2 = ar_scale_exp(__uint_as_float(hdr[1])),
-              s3 = ar_scale_exp(__uint_as_float(hdr[2]));
+    const PackScales ps = pack_scales(a.out, false);
     const int64_t total = ar_pack_floats(d, a.dim);
     const int H = a.H, kbh = d.KBH;
-    // hidden feature of row r of hidden tile t (the 16-feature half tile: 32 KBH + r)
-    auto hid = [&](int t, int r) { return (d.T1 == 2 && t == 2 * kbh) ? 32 * kbh + r : hid_feature(t, r, kbh); };
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
          g += (int64_t)gridDim.x * blockDim.x) {
-        if (g < 256) {
-            if (g == 3) out[g] = __float_as_uint(ldexpf(1.0f, -(s1 + 14)));
-            else if (g == 4) out[g] = __float_as_uint(ldexpf(1.0f, -(s2 + 14)));
-            else if (g == 5) out[g] = __float_as_uint(ldexpf(1.0f, -(s3 + 14)));
-            else if (g >= 8 && g < 8 + d.P) out[g] = __float_as_uint(a.init[g - 8]);
-            else if (g >= 6) out[g] = 0u;
+        if (g < kHdrWords) {
+            write_header_word(out, (int)g, ps, false, a.init, d.P);
             continue;
         }
-        const int64_t w = g - 256;
+        const int64_t w = g - kHdrWords;
         const int64_t s = w / ((int64_t)d.SB * 256);
         const int blk = (int)((w >> 8) - s * d.SB), wl = (int)(w & 255);
         const int i = 1 + (int)(s / d.SPC), u = (int)(s - (int64_t)(i - 1) * d.SPC);
         const float* const* pw = a.w + (int64_t)(i - 1) * 6;
         uint32_t v;
-        if (u < d.NH) {  // layer 1: Linear(2i, H) on the canonical trig order (k = 2j + {cos, sin})
-            const float* W1 = pw[0];
-            const float* b1 = pw[1];
-            const int kb1 = (2 * i + 31) / 32;
-            v = ar_sub_word(
-                d.NS, blk, wl, kb1, 0, d.HT, d.NS * u, ldexpf(1.0f, s1), ldexpf(1.0f, s1 + 14),
-                [&](int t, int r, int k) -> float {
-                    const int f = hid(t, r);
-                    if (f >= H || k >= 2 * i) return 0.0f;
-                    return W1[(int64_t)f * 2 * i + (k & 1) * i + (k >> 1)];  // cat(cos, sin) columns
-                },
-                [&](int t, int r) -> float {
-                    const int f = hid(t, r);
-                    return f < H ? b1[f] : 0.0f;
-                });
-        } else if (u < 2 * d.NH) {  // layer 2: Linear(H, H)
-            const float* W2 = pw[2];
-            const float* b2 = pw[3];
-            v = ar_sub_word(
-                d.NS, blk, wl, kbh, d.T1, d.HT, d.NS * (u - d.NH), ldexpf(1.0f, s2), ldexpf(1.0f, s2 + 14),
-                [&](int t, int r, int k) -> float {
-                    const int f = hid(t, r);
-                    return (f < H && k < H) ? W2[(int64_t)f * H + k] : 0.0f;
-                },
-                [&](int t, int r) -> float {
-                    const int f = hid(t, r);
-                    return f < H ? b2[f] : 0.0f;
-                });
-        } else {  // output layer: Linear(H, 3K-1), row 16 t + r = parameter (W, H, D logits in order)
-            const float* W3 = pw[4];
-            const float* b3 = pw[5];
-            const int P = d.P;
-            v = ar_sub_word(
-                d.NS, blk, wl, kbh, d.T1, d.NO, d.NS * (u - 2 * d.NH), ldexpf(1.0f, s3), ldexpf(1.0f, s3 + 14),
-                [&](int t, int r, int k) -> float {
-                    const int p = 16 * t + r;
-                    return (p < P && k < H) ? W3[(int64_t)p * H + k] : 0.0f;
-                },
-                [&](int t, int r) -> float {
-                    const int p = 16 * t + r;
-                    return p < P ? b3[p] : 0.0f;
-                });
-        }
+        if (u < d.NH)  // layer 1: Linear(2i, H) on the canonical trig order (k = 2j + {cos, sin})
+            v = record_word(d.NS, blk, wl, (2 * i + 31) / 32, 0, d.HT, d.NS * u, ps.sc1, ps.bs1,
+                            HidRows<ColTrig>{pw[0], pw[1], H, 2 * i, kbh, d.T1, ColTrig{i}});
+        else if (u < 2 * d.NH)  // layer 2: Linear(H, H)
+            v = record_word(d.NS, blk, wl, kbh, d.T1, d.HT, d.NS * (u - d.NH), ps.sc2, ps.bs2,
+                            hid_rows(pw[2], pw[3], H, kbh, d.T1));
+        else  // output layer: Linear(H, 3K-1), row 16 t + r = parameter (W, H, D logits in order)
+            v = record_word(d.NS, blk, wl, kbh, d.T1, d.NO, d.NS * (u - 2 * d.NH), ps.sc3, ps.bs3,
+                            OutRows{pw[4], pw[5], 0, d.P, H});
         out[g] = v;
     }
 }
@@ -509,7 +381,7 @@ __device__ __forceinline__ void ar_layer(ArArgs a) {
 
     // ---- prologue: status words, the first two sub-records, the trig operands
     for (int i = threadIdx.x; i < D; i += 64 * kArWaves) cst[i] = 0;
-    const float un1 = a.pack[3], un2 = a.pack[4], un3 = a.pack[5];
+    const float un1 = a.pack[kHdrUnscale], un2 = a.pack[kHdrUnscale + 1], un3 = a.pack[kHdrUnscale + 2];
     h8 th[KBX], tl[KBX];  // layer-1 B operands: features 32 kb + 8 q + j of sample sl
     // the k-blocks this workgroup's conditioners read (a column range of a
     // split launch: conditioners < i_hi read features < 2 (i_hi - 1))
@@ -570,7 +442,7 @@ __device__ __forceinline__ void ar_layer(ArArgs a) {
             // coordinate 0: init_param (flows.py:178-180), the same logits for every sample
             for (int e = lane; e < 16 * P; e += 64) {
                 const int r = e / P;
-                slab[r * PS + (e - r * P)] = a.pack[8 + (e - r * P)];
+                slab[r * PS + (e - r * P)] = a.pack[kHdrInit + (e - r * P)];
             }
         } else {
             const int kb1 = (2 * i + 31) >> 5;
@@ -910,89 +782,36 @@ struct ClPackArgs {
 };
 
 __global__ __launch_bounds__(256) void k_cl_max(ClPackArgs a) {
-    const int64_t n1 = (int64_t)a.H * a.n_lo, n2 = (int64_t)a.H * a.H, n3 = (int64_t)a.n_up * a.d.P * a.H;
-    float m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n1 + n2 + n3;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        if (g < n1)
-            m1 = fmaxf(m1, fabsf(a.w0[g]));
-        else if (g < n1 + n2)
-            m2 = fmaxf(m2, fabsf(a.w2[g - n1]));
-        else
-            m3 = fmaxf(m3, fabsf(a.w4[g - n1 - n2]));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        m1 = fmaxf(m1, __shfl_xor(m1, off, 64));
-        m2 = fmaxf(m2, __shfl_xor(m2, off, 64));
-        m3 = fmaxf(m3, __shfl_xor(m3, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        unsigned int* h = reinterpret_cast<unsigned int*>(a.out);
-        atomicMax(h, __float_as_uint(m1));
-        atomicMax(h + 1, __float_as_uint(m2));
-        atomicMax(h + 2, __float_as_uint(m3));
-    }
+    nfk_absmax3(a.w0, (int64_t)a.H * a.n_lo, a.w2, (int64_t)a.H * a.H, a.w4, (int64_t)a.n_up * a.d.P * a.H, a.out);
 }
 
 __global__ __launch_bounds__(256) void k_cl_pack(ClPackArgs a) {
     const ArDims& d = a.d;
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
-    const unsigned int* hdr = reinterpret_cast<const unsigned int*>(a.out);
-    const int s1 = ar_scale_exp(__uint_as_float(hdr[0])), s2 = ar_scale_exp(__uint_as_float(hdr[1])),
-              s3 = ar_scale_exp(__uint_as_float(hdr[2]));
+    const PackScales ps = pack_scales(a.out, false);
     const int64_t total = cl_pack_floats(d, a.n_up);
-    const int H = a.H, kbh = d.KBH, P = d.P, n_lo = a.n_lo;
-    auto hid = [&](int t, int r) { return (d.T1 == 2 && t == 2 * kbh) ? 32 * kbh + r : hid_feature(t, r, kbh); };
+    const int H = a.H, kbh = d.KBH;
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
          g += (int64_t)gridDim.x * blockDim.x) {
-        if (g < 256) {
-            if (g == 3) out[g] = __float_as_uint(ldexpf(1.0f, -(s1 + 14)));
-            else if (g == 4) out[g] = __float_as_uint(ldexpf(1.0f, -(s2 + 14)));
-            else if (g == 5) out[g] = __float_as_uint(ldexpf(1.0f, -(s3 + 14)));
-            else if (g >= 6) out[g] = 0u;
+        if (g < kHdrWords) {
+            write_header_word(out, (int)g, ps, false);
             continue;
         }
-        const int64_t w = g - 256;
+        const int64_t w = g - kHdrWords;
         const int64_t s = w / ((int64_t)d.SB * 256);
         const int blk = (int)((w >> 8) - s * d.SB), wl = (int)(w & 255);
         uint32_t v;
         if (s < d.NH) {  // layer 1: Linear(n_lo, H) on the lower coordinates in lo_in order
-            v = ar_sub_word(
-                d.NS, blk, wl, a.kb1, 0, d.HT, d.NS * (int)s, ldexpf(1.0f, s1), ldexpf(1.0f, s1 + 14),
-                [&](int t, int r, int k) -> float {
-                    const int f = hid(t, r);
-                    return (f < H && k < n_lo) ? a.w0[(int64_t)f * n_lo + k] : 0.0f;
-                },
-                [&](int t, int r) -> float {
-                    const int f = hid(t, r);
-                    return f < H ? a.b0[f] : 0.0f;
-                });
+            v = record_word(d.NS, blk, wl, a.kb1, 0, d.HT, d.NS * (int)s, ps.sc1, ps.bs1,
+                            HidRows<ColPlain>{a.w0, a.b0, H, a.n_lo, kbh, d.T1, ColPlain{a.n_lo}});
         } else if (s < 2 * d.NH) {  // layer 2: Linear(H, H)
-            v = ar_sub_word(
-                d.NS, blk, wl, kbh, d.T1, d.HT, d.NS * (int)(s - d.NH), ldexpf(1.0f, s2), ldexpf(1.0f, s2 + 14),
-                [&](int t, int r, int k) -> float {
-                    const int f = hid(t, r);
-                    return (f < H && k < H) ? a.w2[(int64_t)f * H + k] : 0.0f;
-                },
-                [&](int t, int r) -> float {
-                    const int f = hid(t, r);
-                    return f < H ? a.b2[f] : 0.0f;
-                });
+            v = record_word(d.NS, blk, wl, kbh, d.T1, d.HT, d.NS * (int)(s - d.NH), ps.sc2, ps.bs2,
+                            hid_rows(a.w2, a.b2, H, kbh, d.T1));
         } else {  // output layer, coordinate j: rows j P + p of Linear(H, n_up P)
             const int64_t u = s - 2 * d.NH;
             const int j = (int)(u / d.N3), part = (int)(u - (int64_t)j * d.N3);
-            const int64_t r0 = (int64_t)j * P;
-            v = ar_sub_word(
-                d.NS, blk, wl, kbh, d.T1, d.NO, d.NS * part, ldexpf(1.0f, s3), ldexpf(1.0f, s3 + 14),
-                [&](int t, int r, int k) -> float {
-                    const int p = 16 * t + r;
-                    return (p < P && k < H) ? a.w4[(r0 + p) * H + k] : 0.0f;
-                },
-                [&](int t, int r) -> float {
-                    const int p = 16 * t + r;
-                    return p < P ? a.b4[r0 + p] : 0.0f;
-                });
+            v = record_word(d.NS, blk, wl, kbh, d.T1, d.NO, d.NS * part, ps.sc3, ps.bs3,
+                            OutRows{a.w4, a.b4, (int64_t)j * d.P, d.P, H});
         }
         out[g] = v;
     }
@@ -1062,7 +881,7 @@ __device__ __forceinline__ void cl_layer(ClArgs a) {
     // ---- prologue: the status word, the lower coordinates (pass-through and
     // the layer-1 operands, scaled per sample), the first two sub-records
     if (threadIdx.x == 0) cst[0] = 0;
-    const float un1 = a.pack[3], un2 = a.pack[4], un3 = a.pack[5];
+    const float un1 = a.pack[kHdrUnscale], un2 = a.pack[kHdrUnscale + 1], un3 = a.pack[kHdrUnscale + 2];
     h8 xh[kClKB1Max], xl[kClKB1Max];
     float c21, bsc1;
     {
@@ -1347,67 +1166,34 @@ __global__ __launch_bounds__(256) void k_ars_pack(ArPackArgs a) {
     const ArDims& d = A.d;
     const int i = 1 + (int)blockIdx.y;  // conditioner
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
-    const unsigned int* hdr = reinterpret_cast<const unsigned int*>(a.out);
-    const int s1 = ar_scale_exp(__uint_as_float(hdr[0])), s2 = ar_scale_exp(__uint_as_float(hdr[1])),
-              s3 = ar_scale_exp(__uint_as_float(hdr[2]));
+    const PackScales ps = pack_scales(a.out, false);
     if (i == 1 && blockIdx.x == 0) {  // the header block
-        for (int g = threadIdx.x; g < 256; g += blockDim.x) {
-            if (g == 3) out[g] = __float_as_uint(ldexpf(1.0f, -(s1 + 14)));
-            else if (g == 4) out[g] = __float_as_uint(ldexpf(1.0f, -(s2 + 14)));
-            else if (g == 5) out[g] = __float_as_uint(ldexpf(1.0f, -(s3 + 14)));
-            else if (g >= 8 && g < 8 + d.P) out[g] = __float_as_uint(a.init[g - 8]);
-            else if (g >= 6) out[g] = 0u;
-        }
+        for (int g = threadIdx.x; g < kHdrWords; g += blockDim.x) write_header_word(out, g, ps, false, a.init, d.P);
     }
     const int H = a.H, kbh = d.KBH, HT = d.HT, kb1 = ars_kb1(i);
     const float* const* pw = a.w + (int64_t)(i - 1) * 6;
-    const float *W1 = pw[0], *b1 = pw[1], *W2 = pw[2], *b2 = pw[3], *W3 = pw[4], *b3 = pw[5];
-    auto hid = [&](int t, int r) { return (d.T1 == 2 && t == 2 * kbh) ? 32 * kbh + r : hid_feature(t, r, kbh); };
+    const HidRows<ColTrig> l1{pw[0], pw[1], H, 2 * i, kbh, d.T1, ColTrig{i}};
     const int64_t base = ars_cond_off(A, i) * 256;
     const int64_t l1w = (int64_t)(1 + kb1 * HT * 2) * 256;
     const int64_t nw = l1w + (int64_t)(d.NH + d.N3) * A.SB2 * 256;
-    const float sc1 = ldexpf(1.0f, s1), bsc1 = ldexpf(1.0f, s1 + 14);
     for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
         const int blk = (int)(w >> 8), wl = (int)(w & 255);
         uint32_t v;
         if (blk == 0) {  // layer-1 bias block [tile][row]
-            const int tt = wl >> 4, r = wl & 15;
-            const int f = tt < HT ? hid(tt, r) : H;
-            v = __float_as_uint(f < H ? b1[f] * bsc1 : 0.0f);
+            const int tt = wl >> 4;
+            v = __float_as_uint(tt < HT ? l1.bias(tt, wl & 15) * ps.bs1 : 0.0f);
         } else if (w < l1w) {  // layer 1, k-block-major: (kb, tile, {hi, lo}), canonical trig order
             const int e = blk - 1, part = e & 1, t = (e >> 1) % HT, kb = (e >> 1) / HT;
-            const int lane = wl >> 2, j = 2 * (wl & 3), k0 = 32 * kb + 8 * (lane >> 4) + j, f = hid(t, lane & 15);
-            auto val = [&](int k) -> float {
-                if (f >= H || k >= 2 * i) return 0.0f;
-                return W1[(int64_t)f * 2 * i + (k & 1) * i + (k >> 1)] * sc1;  // cat(cos, sin) columns
-            };
-            v = nfk_f16_part_pair(val(k0), val(k0 + 1), part);
+            const int lane = wl >> 2, j = 2 * (wl & 3), k0 = 32 * kb + 8 * (lane >> 4) + j;
+            v = nfk_f16_part_pair(l1.val(t, lane & 15, k0) * ps.sc1, l1.val(t, lane & 15, k0 + 1) * ps.sc1, part);
         } else {
             const int rel = (int)((w - l1w) >> 8), sub = rel / A.SB2, b = rel - sub * A.SB2;
-            if (sub < d.NH) {  // layer 2: Linear(H, H)
-                v = ar_sub_word(
-                    d.NS, b, wl, kbh, d.T1, d.HT, d.NS * sub, ldexpf(1.0f, s2), ldexpf(1.0f, s2 + 14),
-                    [&](int t, int r, int k) -> float {
-                        const int f = hid(t, r);
-                        return (f < H && k < H) ? W2[(int64_t)f * H + k] : 0.0f;
-                    },
-                    [&](int t, int r) -> float {
-                        const int f = hid(t, r);
-                        return f < H ? b2[f] : 0.0f;
-                    });
-            } else {  // output layer: Linear(H, 3K-1)
-                const int P = d.P;
-                v = ar_sub_word(
-                    d.NS, b, wl, kbh, d.T1, d.NO, d.NS * (sub - d.NH), ldexpf(1.0f, s3), ldexpf(1.0f, s3 + 14),
-                    [&](int t, int r, int k) -> float {
-                        const int p = 16 * t + r;
-                        return (p < P && k < H) ? W3[(int64_t)p * H + k] : 0.0f;
-                    },
-                    [&](int t, int r) -> float {
-                        const int p = 16 * t + r;
-                        return p < P ? b3[p] : 0.0f;
-                    });
-            }
+            if (sub < d.NH)  // layer 2: Linear(H, H)
+                v = record_word(d.NS, b, wl, kbh, d.T1, d.HT, d.NS * sub, ps.sc2, ps.bs2,
+                                hid_rows(pw[2], pw[3], H, kbh, d.T1));
+            else  // output layer: Linear(H, 3K-1)
+                v = record_word(d.NS, b, wl, kbh, d.T1, d.NO, d.NS * (sub - d.NH), ps.sc3, ps.bs3,
+                                OutRows{pw[4], pw[5], 0, d.P, H});
         }
         out[base + w] = v;
     }
@@ -1537,7 +1323,7 @@ __global__ __launch_bounds__(64 * kArsNW, 1) void k_fused_ar_s(ArsArgs a) {
 
     // ---- prologue: status words, the first NSL sub-records (wait for the first)
     for (int i = threadIdx.x; i < D; i += 64 * NW) cst[i] = 0;
-    const float un1 = a.pack[3], un2 = a.pack[4], un3 = a.pack[5];
+    const float un1 = a.pack[kHdrUnscale], un2 = a.pack[kHdrUnscale + 1], un3 = a.pack[kHdrUnscale + 2];
     stage_next();
     pq0 = stage_next();
     if (kArsNSL > 2) pq1 = stage_next();
@@ -1607,7 +1393,7 @@ __global__ __launch_bounds__(64 * kArsNW, 1) void k_fused_ar_s(ArsArgs a) {
     if (sp == 0) {
         for (int e = lane; e < 16 * P; e += 64) {
             const int r = e / P;
-            scr[r * PS + (e - r * P)] = a.pack[8 + (e - r * P)];
+            scr[r * PS + (e - r * P)] = a.pack[kHdrInit + (e - r * P)];
         }
         cols[0] = 0;
         nc = 1;

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
         c_up = c_lo + A->n_lo;
         sr = 0;
         const FusedConst c = *(const FusedConst*)&A->c;  // by value: SGPRs for the layer
-        const float un1 = pk[3], un2 = pk[4], un3 = pk[5];
+        const float un1 = pk[kHdrUnscale], un2 = pk[kHdrUnscale + 1], un3 = pk[kHdrUnscale + 2];
         bool any_in = false, any_nd = false;
         if (saved && l > 0) {
             // training form: this layer's input (the previous layer's z, in its

@@ -6,14 +6,13 @@
 #include <type_traits>
 
 #include "../../include/nfk.h"
+#include "nfk_mfma.h"
+#include "nfk_pack.h"
 #include "nfk_spline.h"
 
 int nfk_set_error(const char* msg);  // nfk_kernels.hip
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 #ifndef NFK_WAVES
 #define NFK_WAVES 8
@@ -45,40 +44,8 @@ constexpr int kMaxD = 128;
 constexpr int kLdsBytes = 160 * 1024;
 constexpr float kActScale = 16384.0f;  // tanh outputs are split at 2^14 (|h| * 2^14 <= 2^14)
 
-// ---------------------------------------------------------------------------
-// Packed weights ("pack"): a header block, then a stream of phase records.
-// A record is a run of 1-KiB blocks (64 lanes x 16 B, one wave-instruction of
-// global_load_lds each) followed by one bias block (float[16 tiles][16 rows]).
-//   header (1 block): hdr[0..2] = max|W1|, max|W2|, max|W3| (uint bits, from
-//            the pack's reduction); float hdr[3] = 2^-s1, hdr[4] = 2^-(s2+14),
-//            hdr[5] = 2^-(s3+14): the factors undoing the fp16 pre-scaling
-//   f16 blocks (v_mfma_f32_16x16x32_f16, two-way split): k-blocks x NT tiles
-//            x {hi, lo}: lane l of block (kb, t, p) holds part p of
-//            2^s W[row(t, l&15)][32kb + 8(l>>4) + j], j = 0..7, where hi = f16(v),
-//            lo = f16(v - hi) and 2^s puts max|W| in [2^14, 2^15)
-//   tail (T1 only: H = 32 KBH + R, 0 < R <= 4, one v_mfma_f32_16x16x16_f16
-//            per tile): one block per 2 tiles; lane l's 16 B hold tile 2g's
-//            then tile 2g + 1's fragment, 4 halves over the tail features
-//            32 KBH + 0..3 of row(t, l&15): k-group l>>4 = {hi, hi, lo, 0} of 2^s W, against
-//            the B groups {a_hi, a_lo, a_hi, -} (tail_word, act_operands): the
-//            same three split products as the k-blocks, in one f16 MFMA
-//   layer 1: KB1 = ceil(n_lo/32) f16 k-blocks (x is scaled per sample, by a power of two), bias unscaled
-//   layer 2: KBH f16 k-blocks (+ tail blocks), bias pre-scaled by 2^(s2+14)
-//   per 16-coordinate chunk: W logits (K tiles), H logits (K tiles), D logits
-//            (K-1 tiles), same form; row i of tile t = parameter t of coordinate 16c+i
-// Hidden feature permutation: row i of hidden tile t < 2 KBH computes feature
-//   f(t, i) = 32(t>>1) + 8(i>>2) + 4(t&1) + (i&3),
-// so accumulator register r of tiles 2kb, 2kb+1 of lane l are exactly
-// elements j = r, 4 + r of the next product's B fragment for k-block kb
-// (k = 32kb + 8(l>>4) + j) -- activations never leave registers.  With a
-// tail, tile 2 KBH holds features 32 KBH + r in register r of every lane
-// group (rows duplicated): the B operand of the tail step needs all R in
-// each lane.
-// wide = 1 (nfk_fused_wide.h): the output layer in 8-coordinate chunks whose
-//   W/H/D records have ceil(K/2) tiles; row i of tile t = parameter
-//   2t + (i&1) of coordinate 8c + 2(i>>2) + ((i>>1)&1), so lane group q holds
-//   two coordinates with all their parameters in registers 2h, 2h+1 of the
-//   tiles (half the accumulators of the 16-coordinate form).
+// The pack format (header, records, hidden feature permutation): nfk_pack.h.
+
 // Diagnostic timeline (-DNFK_TRACE builds only, tools/trace_wide.py): each
 // wave records s_memtime at marked points into lanes of 4 VGPRs (256 marks);
 // every 512th workgroup writes them to a buffer set by nfk_debug_trace().
@@ -222,38 +189,6 @@ inline int chain_max_layers(const Layout& L) {
     return n;
 }
 
-// hidden feature computed by row i (0..15) of hidden tile t (>= H: padding)
-__host__ __device__ inline int hid_feature(int t, int i, int kbh) {
-    if (t < 2 * kbh) return 32 * (t >> 1) + 8 * (i >> 2) + 4 * (t & 1) + (i & 3);
-    return 32 * kbh + (i & 3);  // the tail tile: every lane group holds the tail features
-}
-
-// f16 pair (v0, v1) of split part p (0 = hi, 1 = lo) as one packed word
-__device__ __forceinline__ uint32_t nfk_f16_part_pair(float v0, float v1, int part) {
-    const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-    const _Float16 r0 = part ? (_Float16)(v0 - (float)h0) : h0;
-    const _Float16 r1 = part ? (_Float16)(v1 - (float)h1) : h1;
-    return (uint32_t)__builtin_bit_cast(uint16_t, r0) | ((uint32_t)__builtin_bit_cast(uint16_t, r1) << 16);
-}
-
-// Word wl (0..255) of tail block g of a record with nt tiles (the 16x16x16 f16
-// A fragments of tiles 2g and 2g + 1, interleaved per lane: words 4l, 4l + 1
-// tile 2g, 4l + 2, 4l + 3 tile 2g + 1): lane l of tile t holds halves j = 0..3 =
-// tail features kbase + j of weight row row_of(t, l & 15), as the hi part in
-// k-groups 0 and 1, the lo part in k-group 2, zero in k-group 3.
-template <class RowF>
-__device__ uint32_t tail_word(int g, int wl, int nt, int kbase, int H, float sc, RowF row_of) {
-    const int t = 2 * g + ((wl & 3) >> 1), lane = wl >> 2, j = 2 * (wl & 1), q = lane >> 4;
-    if (t >= nt || q == 3) return 0u;
-    const float* w = row_of(t, lane & 15);
-    float v0 = 0.0f, v1 = 0.0f;
-    if (w != nullptr) {
-        if (kbase + j < H) v0 = w[kbase + j] * sc;
-        if (kbase + j + 1 < H) v1 = w[kbase + j + 1] * sc;
-    }
-    return nfk_f16_part_pair(v0, v1, q == 2 ? 1 : 0);
-}
-
 // Spline constants of NSF_CL (flows.py:236: left = bottom = -B, right = top = B,
 // default min bin width = height = derivative = 1e-3), one set for x and y.
 struct FusedConst {
@@ -299,15 +234,6 @@ struct FusedArgs {
     const int32_t* smaps;
 };
 
-__device__ __forceinline__ f32x4 mfma16(h8 a, h8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// the tail step: K = 16 over the packed (hi, hi, lo, 0) x (a_hi, a_lo, a_hi, -) groups
-__device__ __forceinline__ f32x4 mfma16k16(h4 a, h4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ f32x4 as_f32x4(const float4& v) {
     f32x4 r;
     r[0] = v.x;
@@ -317,27 +243,7 @@ __device__ __forceinline__ f32x4 as_f32x4(const float4& v) {
     return r;
 }
 
-// LDS-DMA is issued through inline asm and waited for by hand: the compiler
-// cannot prove that a DMA into one slot does not alias reads of the other, so
-// with the builtin it drains every DMA (vmcnt(0)) before the first ds_read of
-// each phase -- serialising the copy of phase p+1 with the compute of phase p.
-// Invariant instead: a DMA issued right after the barrier that ends phase p
-// is waited for (vmcnt(0)) at the barrier that ends phase p+1, and the kernel
-// issues no other VGPR-destination global loads while DMAs are in flight.
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-
-__device__ __forceinline__ void dma16(const float* gsrc, uint32_t lds) {
-    uint32_t saved;  // m0 is reserved by the compiler: restore it
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(saved)
-                 : "s"(__builtin_amdgcn_readfirstlane(lds)), "v"(gsrc)
-                 : "memory");
-}
-
-// The same from a WAVE-UNIFORM source address: the saddr form (SGPR base +
+// dma16 (nfk_mfma.h) from a WAVE-UNIFORM source address: the saddr form (SGPR base +
 // a 32-bit per-lane VGPR offset), so stepping the source costs two SALU adds
 // instead of a 64-bit VALU add per lane and block.  Off by default: measured
 // 3 % SLOWER on the c3 chain (5.57 vs 5.39-5.42 ms per launch, A/B on one box,
@@ -1204,7 +1110,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF
         sr = 0;
     }
     const FusedConst c = *(const FusedConst*)&A->c;  // by value (SGPRs); per layer: see A
-    const float un1 = pk[3], un2 = pk[4], un3 = pk[5];
+    const float un1 = pk[kHdrUnscale], un2 = pk[kHdrUnscale + 1], un3 = pk[kHdrUnscale + 2];
         bool any_in = false, any_nd = false;
 
         // layer-1 B operand of k-block kb: lower coordinates 32 kb + 8 q .. + 7 of

@@ -78,12 +78,6 @@ inline size_t lds_bytes(const RLayout& L) {
     return 2 * (size_t)L.slot_blocks * 1024 + (size_t)kWaves * 16 * tile_row(L) * sizeof(float);
 }
 
-// input coordinate of k-slot 32 kb + 8 q + j of a layer-1 B fragment
-__host__ __device__ inline int in_perm(int k) {
-    const int kb = k >> 5, q = (k >> 3) & 3, j = k & 7;
-    return 32 * kb + 16 * (j >> 2) + 4 * q + (j & 3);
-}
-
 struct RArgs {
     const float* x;
     const float* pack;
@@ -149,8 +143,8 @@ __global__ __launch_bounds__(64 * kWaves, 1) void k_fused_rnvp(RArgs a) {
         const int tg_off = pr == 0 ? XI : 0;
         const int b = 4 * hk;
         const float4* s_l1 = ((b & 1) ? slot1 : slot0);
-        // header: per (pair, net, layer) unscale factors at hdr[16 + (2 pr + net) 3 + layer]
-        const float* un = hdr + 16 + pr * 6;
+        // header: per (pair, net, layer) unscale factors at hdr[kHdrRnvpUnscale + (2 pr + net) 3 + layer]
+        const float* un = hdr + kHdrRnvpUnscale + pr * 6;
 
         // ---- phase 0: layer 1 of s and t from the (per-sample scaled) input half
         h8 bsh[KBH], bsl[KBH], bth[KBH], btl[KBH];
@@ -263,72 +257,26 @@ __global__ __launch_bounds__(256) void k_rnvp_max(RPackArgs a) {
     // hdr[(2 pr + net) 3 + layer] = max |W| of that net layer (uint bits)
     const RLayout& L = a.L;
     const int64_t sz[3] = {(int64_t)L.H * L.n, (int64_t)L.H * L.H, (int64_t)L.n * L.H};
-    for (int m = 0; m < 12; ++m) {
-        const float* w = a.w[(m / 3) * 6 + 2 * (m % 3)];
-        const int64_t cnt = sz[m % 3];
-        float mx = 0.0f;
-        for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < cnt;
-             g += (int64_t)gridDim.x * blockDim.x)
-            mx = fmaxf(mx, fabsf(w[g]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(a.out) + m, __float_as_uint(mx));
-    }
-}
-
-__device__ inline int rscale_exp(float maxw) {
-    if (!(maxw > 0.0f) || !(maxw < 3.0e38f)) return 0;
-    int e;
-    frexpf(maxw, &e);
-    return 15 - e;
-}
-
-__device__ inline uint32_t f16_pair(float v0, float v1, int part) {
-    const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
-    const _Float16 r0 = part ? (_Float16)(v0 - (float)h0) : h0;
-    const _Float16 r1 = part ? (_Float16)(v1 - (float)h1) : h1;
-    return (uint32_t)__builtin_bit_cast(uint16_t, r0) | ((uint32_t)__builtin_bit_cast(uint16_t, r1) << 16);
-}
-
-// word wl of block blk of a gemm_h-form record (f16 blocks, tail blocks, bias)
-// with nt tiles; rows: weight row pointer (or null) per (tile, row)
-template <class RowF, class BiasF>
-__device__ uint32_t rec_word(int blk, int wl, const RLayout& L, int nt, float sc, float bsc, RowF row_of,
-                             BiasF bias_of) {
-    const int nf = L.KBH * nt * 2, ntg = L.T1 ? (nt + 1) / 2 : 0;
-    if (blk < nf) {
-        const int part = blk & 1, idx = blk >> 1, kb = idx / nt, t = idx - kb * nt;
-        const int lane = wl >> 2, j = 2 * (wl & 3), k0 = 32 * kb + 8 * (lane >> 4) + j;
-        const float* w = row_of(t, lane & 15);
-        const int klim = L.T1 ? 32 * L.KBH : L.H;
-        float v0 = 0.0f, v1 = 0.0f;
-        if (w != nullptr) {
-            if (k0 < klim && k0 < L.H) v0 = w[k0] * sc;
-            if (k0 + 1 < klim && k0 + 1 < L.H) v1 = w[k0 + 1] * sc;
-        }
-        return f16_pair(v0, v1, part);
-    }
-    if (blk < nf + ntg) return tail_word(blk - nf, wl, nt, 32 * L.KBH, L.H, sc, row_of);
-    const int t = wl >> 4, i = wl & 15;
-    return __float_as_uint(t < nt ? bias_of(t, i) * bsc : 0.0f);
+    for (int m = 0; m < 12; ++m)
+        nfk_absmax(a.w[(m / 3) * 6 + 2 * (m % 3)], sz[m % 3], reinterpret_cast<unsigned int*>(a.out) + kHdrMax + m);
 }
 
 __global__ __launch_bounds__(256) void k_rnvp_pack(RPackArgs a) {
     const RLayout& L = a.L;
-    const unsigned int* hmax = reinterpret_cast<const unsigned int*>(a.out);
+    const unsigned int* hmax = reinterpret_cast<const unsigned int*>(a.out) + kHdrMax;
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out);
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < L.total;
          g += (int64_t)gridDim.x * blockDim.x) {
-        if (g < 256) {  // header: words 16 + m = unscale of net layer m
-            if (g >= 16 && g < 28) {
-                const int m = (int)g - 16, s = rscale_exp(__uint_as_float(hmax[m]));
+        if (g < kHdrWords) {  // header: the unscale of net layer m, zeros behind the maxima
+            if (g >= kHdrRnvpUnscale && g < kHdrRnvpUnscale + 12) {
+                const int m = (int)g - kHdrRnvpUnscale, s = nfk_scale_exp(__uint_as_float(hmax[m]));
                 out[g] = __float_as_uint(ldexpf(1.0f, (m % 3 == 0) ? -s : -(s + 14)));
             } else if (g >= 12) {
                 out[g] = 0;
             }
             continue;
         }
-        const int64_t w = g - 256;
+        const int64_t w = g - kHdrWords;
         const int pr = (int)(w / ((int64_t)L.pair_blocks * 256));
         int blk = (int)((w >> 8) - (int64_t)pr * L.pair_blocks);
         const int wl = (int)(w & 255);
@@ -350,48 +298,15 @@ __global__ __launch_bounds__(256) void k_rnvp_pack(RPackArgs a) {
         }
         const int m = (2 * pr + net) * 3 + layer;
         const float* const* W = a.w + (2 * pr + net) * 6;
-        const int s = rscale_exp(__uint_as_float(hmax[m]));
-        const float sc = ldexpf(1.0f, s);
-        const int kbh = L.KBH;
-        if (layer == 0) {  // input GEMM: f16 blocks over the permuted input coordinates + unscaled bias
-            if (blk < L.KBI * L.HT * 2) {
-                const int part = blk & 1, idx = blk >> 1, kb = idx / L.HT, t = idx - kb * L.HT;
-                const int lane = wl >> 2, j = 2 * (wl & 3);
-                const int f = hid_feature(t, lane & 15, kbh), k0 = 32 * kb + 8 * (lane >> 4) + j;
-                const int c0 = in_perm(k0), c1 = in_perm(k0 + 1);
-                float v0 = 0.0f, v1 = 0.0f;
-                if (f < L.H) {
-                    if (c0 < L.n) v0 = W[0][(int64_t)f * L.n + c0] * sc;
-                    if (c1 < L.n) v1 = W[0][(int64_t)f * L.n + c1] * sc;
-                }
-                out[g] = f16_pair(v0, v1, part);
-            } else {
-                const int t = wl >> 4, f = hid_feature(t, wl & 15, kbh);
-                out[g] = __float_as_uint((t < L.HT && f < L.H) ? W[1][f] : 0.0f);
-            }
-        } else if (layer == 1) {
-            out[g] = rec_word(
-                blk, wl, L, L.HT, sc, ldexpf(1.0f, s + 14),
-                [&](int t, int i) -> const float* {
-                    const int f = hid_feature(t, i, kbh);
-                    return f < L.H ? W[2] + (int64_t)f * L.H : nullptr;
-                },
-                [&](int t, int i) -> float {
-                    const int f = hid_feature(t, i, kbh);
-                    return f < L.H ? W[3][f] : 0.0f;
-                });
-        } else {
-            out[g] = rec_word(
-                blk, wl, L, L.NO, sc, ldexpf(1.0f, s + 14),
-                [&](int t, int i) -> const float* {
-                    const int c = 16 * t + i;
-                    return c < L.n ? W[4] + (int64_t)c * L.H : nullptr;
-                },
-                [&](int t, int i) -> float {
-                    const int c = 16 * t + i;
-                    return c < L.n ? W[5][c] : 0.0f;
-                });
-        }
+        const int s = nfk_scale_exp(__uint_as_float(hmax[m]));
+        const float sc = ldexpf(1.0f, s), bsc = ldexpf(1.0f, s + 14);
+        if (layer == 0)  // input GEMM: f16 blocks over the permuted input coordinates + unscaled bias
+            out[g] = record_word(L.HT, blk, wl, L.KBI, 0, L.HT, 0, sc, 1.0f,
+                                 HidRows<ColPerm>{W[0], W[1], L.H, L.n, L.KBH, L.T1, ColPerm{L.n}});
+        else if (layer == 1)
+            out[g] = record_word(L.HT, blk, wl, L.KBH, L.T1, L.HT, 0, sc, bsc, hid_rows(W[2], W[3], L.H, L.KBH, L.T1));
+        else
+            out[g] = record_word(L.NO, blk, wl, L.KBH, L.T1, L.NO, 0, sc, bsc, OutRows{W[4], W[5], 0, L.n, L.H});
     }
 }
 
@@ -610,7 +525,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_rnvp_chain(RChainArgs a) 
             const int pr = INV ? 1 - hk : hk;     // net pair of this half: 0 = (s1, t1), 1 = (s2, t2)
             const int in_off = pr == 0 ? 0 : XI;  // pair 0 reads the lower half, updates the upper
             const int tg_off = pr == 0 ? XI : 0;
-            const float* un = hdr + 16 + pr * 6;  // unscale factors of (net, layer) in the pair
+            const float* un = hdr + kHdrRnvpUnscale + pr * 6;  // unscale factors of (net, layer) in the pair
             // layer-1 operands of the input half, per-sample power-of-two scaled (as k_fused_rnvp)
             h8 xh[KBI], xl[KBI];
             int ex = 0;

@@ -12,7 +12,7 @@
 // round trip into nfk_rqs_coupling_bwd.
 //
 // Layout: the output layer in 8-coordinate chunks (the wide record layout,
-// nfk_fused_impl.h: lane group q holds coordinates 8c + 2q, 8c + 2q + 1 with
+// nfk_pack.h: lane group q holds coordinates 8c + 2q, 8c + 2q + 1 with
 // ALL their parameters in registers 2h, 2h + 1 of the W, H and D tiles), so
 // one lane has every logit of its two coordinates at once for the element
 // backward.  The records are re-cut into kVNS-tile sub-records of SB blocks
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     int cur = 0;
-    const float un1 = a.hdr[3], un2 = a.hdr[4], un3 = a.hdr[5];
+    const float un1 = a.hdr[kHdrUnscale], un2 = a.hdr[kHdrUnscale + 1], un3 = a.hdr[kHdrUnscale + 2];
 
     // ---- layer 1 (one k-block: n_lo <= 32), per-sample power-of-two scaled x (each row its own exponent: rows stay independent)
     h8 bh[KBH], bl[KBH];

@@ -32,7 +32,7 @@
 //     against 1.2 / 3.7 GB (profiles/r3e_pmc_c5.txt);
 //   * LDS: two 65-KiB slots + 2 KiB x tile per wave + index maps (152 KiB at
 //     c5), one 8-wave workgroup (128 samples) per CU.
-// Copies follow the invariant of nfk_fused_impl.h: a copy is waited for
+// Copies follow the invariant of nfk_mfma.h: a copy is waited for
 // (vmcnt(0)) at the barrier ending the sub-step after the one it was issued
 // in, and the loop issues no VGPR-destination global load.
 #pragma once
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(64 * kWideWaves, kWideWGs) void k_fused_nsf_wide(Wi
         m_lo_in[i] = a.lo_in[i];
         m_lo_out[i] = a.lo_out[i];
     }
-    const float un1 = pk[3], un2 = pk[4], un3 = pk[5];
+    const float un1 = pk[kHdrUnscale], un2 = pk[kHdrUnscale + 1], un3 = pk[kHdrUnscale + 2];
     __syncthreads();
     int s = 0;
     wide_stage<KBH, K, INV>(a, 0, slot0, slot1, wid, lane);

@@ -41,13 +41,11 @@
 #include <cstdlib>
 
 #include "../../include/nfk.h"
+#include "nfk_mfma.h"
 
 int nfk_set_error(const char* msg);  // nfk_kernels.hip
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // GEMM workgroup shapes (waves NW, output tiles per wave NTW, k-blocks of
 // weights in flight per wave PF; 8 output tiles per workgroup either way): see
@@ -69,25 +67,6 @@ int wl_status(const char* what) {
         return (int)e;
     }
     return 0;
-}
-
-__device__ __forceinline__ f32x4 mfma16(h8 a, h8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-
-// one 16-byte LDS-DMA per lane (global_load_lds_dwordx4; m0 = the LDS base of
-// the wave's 1-KiB block, restored after: the compiler reserves m0)
-__device__ __forceinline__ void dma16(const float4* gsrc, uint32_t lds) {
-    uint32_t saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(saved)
-                 : "s"(__builtin_amdgcn_readfirstlane(lds)), "v"(gsrc)
-                 : "memory");
 }
 
 // ---------------------------------------------------------------------------
@@ -175,7 +154,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_wl_gemm(WlGemm a) {
         for (int d = 0; d < D; ++d) {
             const int blk = wid + kWlWaves * d < XB ? wid + kWlWaves * d : XB - 1;  // (wave-uniform)
             const int s = blk >> 1, part = blk & 1;
-            dma16(xg + ((int64_t)(s * a.KB + kb0 + kx) * 2 + part) * 64 + lane, slot + (uint32_t)(blk * 1024));
+            dma16(reinterpret_cast<const float*>(xg + ((int64_t)(s * a.KB + kb0 + kx) * 2 + part) * 64 + lane),
+                  slot + (uint32_t)(blk * 1024));
         }
         // (a wave-uniform offset select, not a branch)
         const int64_t live = kk < nkc ? 1 : 0;
