@@ -31,7 +31,7 @@ extern "C" {
 
 typedef void* nfk_stream_t; /* hipStream_t */
 
-#define NFK_ABI_VERSION 2
+#define NFK_ABI_VERSION 3
 #define NFK_EINVAL (-1)
 
 /* status bits, OR-ed into *status by the kernels */
@@ -547,6 +547,83 @@ int nfk_ar_seqinv(const float* z, int64_t ldz, const float* const* weights, cons
                   int32_t hidden, int32_t K, double tail_bound, float* x, int64_t ldx, float* logdet,
                   int32_t logdet_mode, int64_t batch, int32_t* status, float* workspace, int64_t workspace_floats,
                   nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Priors and targets of the applications layer (applications/src/systems.py),
+ * nfk_systems.hip.  No MFMA, no atomics on floats: every sum has a fixed
+ * order, so two runs are bitwise equal.
+ *
+ * Einstein crystal (systems.py:366-372): per row, with D = natoms * dim and
+ * centers [natoms, dim] dense,
+ *   dev_c = z_c - centers_c;  has_box: dev_c -= (|dev_c| > (float)(0.5 L)) sign(dev_c) (float)L
+ *   out[b] = -0.5*(D*log(2pi) + sum_c (dev_c/scale)^2) - natoms*half_log_det
+ *            + sign * logdet[b]          (logdet nullable; sign = +1 or -1)
+ * scale = sqrt(1/alpha) and half_log_det = dim*log(scale) are those of the
+ * per-atom MultivariateNormal(0, I/alpha) as torch evaluates them (the
+ * constants of nfk_normal_logprob, per atom).  boxlength is L (a double, as
+ * the reference's Python scalar); has_box = 0 skips the wrap.
+ *   status: nullable; NFK_ST_NAN_Z is OR-ed in when a row of z holds a NaN.
+ * Rows that are 16-byte aligned with D % 4 == 0 take a float4 form
+ * (y = dev * (1/scale): <= 1 ulp per element from the scalar form's dev/scale).
+ * Backward: gz[b, c] = -dev_c / scale^2 * g[b] (the wrap has zero derivative).
+ * ------------------------------------------------------------------------- */
+int nfk_einstein_logprob(const float* z, int64_t ldz, const float* centers, const float* logdet,
+                         float* out, int64_t batch, int32_t natoms, int32_t dim, float scale,
+                         float half_log_det, int32_t has_box, double boxlength, int32_t sign,
+                         int32_t* status, nfk_stream_t stream);
+int nfk_einstein_logprob_bwd(const float* z, int64_t ldz, const float* centers, const float* g,
+                             float* gz, int64_t ldgz, int64_t batch, int32_t natoms, int32_t dim,
+                             float scale, int32_t has_box, double boxlength, nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Gaussian mixture (systems.py:287-292): a row holds npart particles of dim
+ * coordinates; centers [ncenters, dim], scales [ncenters] (sqrt(var_i), the
+ * components' Cholesky diagonals) and hlds [ncenters] (dim*log(scale_i)) dense.
+ *   p(x)   = sum_i (float)(1/ncenters) * exp(-0.5*(dim*log(2pi) + |(x-c_i)/scale_i|^2) - hld_i)
+ *            accumulated in centre order with accurate expf (not a log-sum-exp:
+ *            a particle far from every centre gives log(0) = -inf, as the
+ *            reference does)
+ *   out[b] = sum_particles log p(x) + sign * logdet[b]
+ *   status: nullable; NFK_ST_NAN_Z on a NaN row.
+ * Backward: gx = g[b] * sum_i p_i * (-(x-c_i)/var_i) / p(x) (NaN where p(x) == 0,
+ * as torch's autograd gives).
+ * Supported shapes: nfk_gmix_supported() != 0 (ncenters <= 64, dim <= 4).
+ * ------------------------------------------------------------------------- */
+int nfk_gmix_supported(int32_t ncenters, int32_t dim);
+int nfk_gmix_logprob(const float* x, int64_t ldx, const float* centers, const float* scales,
+                     const float* hlds, const float* logdet, float* out, int64_t batch,
+                     int32_t npart, int32_t dim, int32_t ncenters, int32_t sign, int32_t* status,
+                     nfk_stream_t stream);
+int nfk_gmix_logprob_bwd(const float* x, int64_t ldx, const float* centers, const float* scales,
+                         const float* hlds, const float* g, float* gx, int64_t ldgx, int64_t batch,
+                         int32_t npart, int32_t dim, int32_t ncenters, nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Lennard-Jones energy of a periodic box (LJ.potential, systems.py:154-189),
+ * x [batch, n*dim] rows of n particles, with the reference's arithmetic: per
+ * pair (i, j), i != j included twice and the diagonal too,
+ *   d_c = x_ic - x_jc;  d_c -= (|d_c| > (float)(0.5 L)) sign(d_c) (float)L   (one wrap)
+ *   r = |d|;  inv = 1/(r + (r == 0));  has_cutoff: inv = 0 where r > cutoff
+ *   p6 = (sigma*inv)^6;  u = 4 epsilon (p6^2 - p6 [- s6^2 + s6 with has_cutoff and shift,
+ *   s6 = (sigma/cutoff)^6]);  u *= inv * r  (zero on the diagonal, for coincident
+ *   pairs and beyond the cutoff)
+ *   out[b] = sum_ij u / 2
+ * n <= 64: a row takes a group of next_pow2(n) lanes (64 / group rows per
+ * wave); 64 < n <= 256: one row per wave.  Lane i keeps particle i (and i + 64,
+ * ...) in registers and walks j through the row staged in LDS (one broadcast
+ * read per j), so no [n, n] temporary exists; the row's energy is a fixed-order
+ * sum.  Backward: gx[b, i] = g[b] * sum_j u'(r_ij) d_ij / r_ij (the force on i,
+ * negated), each lane summing its own particle: no atomics.
+ * Supported shapes: nfk_lj_supported() != 0 (n <= 256, dim 2 or 3).
+ * ------------------------------------------------------------------------- */
+int nfk_lj_supported(int32_t n, int32_t dim);
+int nfk_lj_potential(const float* x, int64_t ldx, float* out, int64_t batch, int32_t n, int32_t dim,
+                     double boxlength, double sigma, double epsilon, int32_t has_cutoff,
+                     double cutoff, int32_t shift, nfk_stream_t stream);
+int nfk_lj_potential_bwd(const float* x, int64_t ldx, const float* g, float* gx, int64_t ldgx,
+                         int64_t batch, int32_t n, int32_t dim, double boxlength, double sigma,
+                         double epsilon, int32_t has_cutoff, double cutoff, int32_t shift,
+                         nfk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -5,8 +5,11 @@ Public surface mirrors the reference (re-exported as the ``nf`` package):
     from nf.flows import RealNVP, NSF_CL, NSF_AR, Planar, Radial, FCNN
     from nf.models import NormalizingFlowModel   # also NormalizingFlow
     from nf.utils import unconstrained_RQS, RQS, searchsorted
+The applications' priors and targets (applications/src/systems.py):
+    from normalizingflow_amd.systems import EinsteinCrystal, GaussianMixture, LJ
 """
 from . import config  # noqa: F401
+from . import systems  # noqa: F401
 from ._lib import LIB_PATH, load as load_library  # noqa: F401
 from .flows import FCNN, NSF_AR, NSF_CL, Planar, Radial, RealNVP  # noqa: F401
 from .flows import MAF, ActNorm, OneByOneConv  # noqa: F401

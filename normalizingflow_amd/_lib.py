@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NFK_LIBRARY", os.path.join(_HERE, "libnfk.so"))
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 NFK_EINVAL = -1
 ST_INSIDE_SEEN = 1
@@ -167,6 +167,30 @@ SIGNATURES = {
         P, I64, P, I32,                 # z, ldz, logdet, logdet_mode
         I64, I32, P,                    # batch, inverse, status
         P, F32, F32, P]),               # log_prob, prior_scale, prior_half_log_det, stream
+    "nfk_einstein_logprob": (ctypes.c_int, [
+        P, I64, P, P, P,                # z, ldz, centers, logdet, out
+        I64, I32, I32, F32, F32,        # batch, natoms, dim, scale, half_log_det
+        I32, F64, I32, P, P]),          # has_box, boxlength, sign, status, stream
+    "nfk_einstein_logprob_bwd": (ctypes.c_int, [
+        P, I64, P, P, P, I64,           # z, ldz, centers, g, gz, ldgz
+        I64, I32, I32, F32,             # batch, natoms, dim, scale
+        I32, F64, P]),                  # has_box, boxlength, stream
+    "nfk_gmix_supported": (ctypes.c_int, [I32, I32]),
+    "nfk_gmix_logprob": (ctypes.c_int, [
+        P, I64, P, P, P, P, P,          # x, ldx, centers, scales, hlds, logdet, out
+        I64, I32, I32, I32,             # batch, npart, dim, ncenters
+        I32, P, P]),                    # sign, status, stream
+    "nfk_gmix_logprob_bwd": (ctypes.c_int, [
+        P, I64, P, P, P, P, P, I64,     # x, ldx, centers, scales, hlds, g, gx, ldgx
+        I64, I32, I32, I32, P]),        # batch, npart, dim, ncenters, stream
+    "nfk_lj_supported": (ctypes.c_int, [I32, I32]),
+    "nfk_lj_potential": (ctypes.c_int, [
+        P, I64, P, I64, I32, I32,       # x, ldx, out, batch, n, dim
+        F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_lj_potential_bwd": (ctypes.c_int, [
+        P, I64, P, P, I64,              # x, ldx, g, gx, ldgx
+        I64, I32, I32,                  # batch, n, dim
+        F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
 }
 
 _lock = threading.Lock()

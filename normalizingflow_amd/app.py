@@ -7,9 +7,14 @@ restated for the flow path.
   merging a key the defaults do not define raises ``KeyError``.
 * ``build_flows`` / ``build_model`` -- the flow construction of
   setup.py:37-63 (RealNVP / NSF_AR / NSF_CL with the reference's tail bound B
-  and NSF_CL mask cycle), the "Normal" prior of setup.py:25-30.  Other
-  potentials/priors (LJ, Fe, Einstein crystal, Gaussian mixtures) belong to
-  the physics layer and are out of scope.
+  and NSF_CL mask cycle) and the priors of setup.py:17-30: "Normal",
+  "EinsteinCrystal" and "GaussianMixture" (systems.py).
+* ``build_potential`` -- the target distribution of setup.py:76-80
+  (EinsteinCrystal, GaussianMixture, LJ); the LAMMPS-backed Fe and SimData
+  are out of scope.
+* ``reverse_kl`` / ``forward_kl`` -- the losses of setup.py:90-100;
+  ``q_matrix`` -- the Q matrix of test.py:33-50 (generate_from_nf, evaluate
+  and the target's energies), up to ``Q = torch.stack(...)``.
 * ``save_checkpoint`` / ``load_checkpoint`` -- the checkpoint dict of
   train.py:39-40 and the loader of setup.py:102-109 (``load_state_dict``
   with ``strict=False``), read with ``torch.load(weights_only=True)``.
@@ -23,10 +28,12 @@ import torch
 import yaml
 
 from . import flows as F_
+from . import systems
 from .models import NormalizingFlowModel
 
 __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flows", "build_prior",
-           "build_model", "save_checkpoint", "load_checkpoint", "train_step"]
+           "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
+           "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix"]
 
 
 class CfgNode(dict):
@@ -138,16 +145,47 @@ def build_flows(cfg):
     raise ValueError("flow type %r is not built by setup.py" % fl.type)
 
 
+def _parse_potential(name, c, device, what):
+    """setup.py:17-36 for the distributions this package builds."""
+    if name == "GaussianMixture":
+        return systems.GaussianMixture(c.centers, c.vars, c.nparticles, c.dim, device=device)
+    if name == "EinsteinCrystal":
+        return systems.EinsteinCrystal(c.centers, c.dim, boxlength=c.boxlength, alpha=c.alpha, device=device)
+    if name == "Normal":
+        N = c.nparticles * c.dim
+        var = 1 if c.vars is None else c.vars
+        return torch.distributions.MultivariateNormal(torch.zeros(N, device=device),
+                                                      var * torch.eye(N, device=device))
+    if name == "LJ" and what == "potential":
+        return systems.LJ(pos_dir=c.data, boxlength=c.boxlength, device=device, sigma=c.sigma,
+                          epsilon=c.epsilon, cutoff=c.cutoff, shift=c.shift)
+    raise NotImplementedError("%s %r is not built here (systems.py holds EinsteinCrystal, GaussianMixture "
+                              "and LJ; LAMMPS-backed Fe and SimData are out of scope); pass an object "
+                              "instead" % (what, name))
+
+
 def build_prior(cfg, device):
-    """The "Normal" prior of setup.py:25-30."""
-    p = cfg.prior
-    if p.type != "Normal":
-        raise NotImplementedError("prior %r lives in the physics layer (out of scope); pass a "
-                                  "prior object to build_model" % p.type)
-    N = p.nparticles * p.dim
-    var = 1 if p.vars is None else p.vars
-    return torch.distributions.MultivariateNormal(torch.zeros(N, device=device),
-                                                  var * torch.eye(N, device=device))
+    """The "Normal", "EinsteinCrystal" and "GaussianMixture" priors of
+    setup.py:17-30 from ``cfg.prior``."""
+    if cfg.prior.type == "LJ":
+        raise NotImplementedError("prior 'LJ' has no log_prob; pass a prior object to build_model")
+    return _parse_potential(cfg.prior.type, cfg.prior, device, "prior")
+
+
+def build_potential(cfg, mode="training", device=None):
+    """The target of setup.py:76-80: ``cfg.dataset.data`` is set from
+    training_data / testing_data by ``mode``, then ``cfg.dataset.potential``
+    (EinsteinCrystal, GaussianMixture, LJ or Normal) is built from
+    ``cfg.dataset``.  As in setup_model, a missing ``dataset.boxlength``
+    becomes 2 B first."""
+    device = cfg.device if device is None else device
+    if cfg.dataset.boxlength is None and tail_bound(cfg) is not None:
+        cfg.dataset.boxlength = 2 * tail_bound(cfg)
+    if mode == "training":
+        cfg.dataset.data = cfg.dataset.training_data
+    elif mode == "testing":
+        cfg.dataset.data = cfg.dataset.testing_data
+    return _parse_potential(cfg.dataset.potential, cfg.dataset, device, "potential")
 
 
 def build_model(cfg, prior=None, device=None):
@@ -190,3 +228,53 @@ def train_step(model, optimizer, x, scheduler=None):
     if scheduler is not None:
         scheduler.step()
     return loss.detach()
+
+
+def reverse_kl(model, potential, nsamples):
+    """setup.py:90-94 (reverseKL): prior samples pushed through the inverse
+    flow, scored by the target."""
+    z = model.prior.sample((nsamples,))
+    x, log_det = model.inverse(z)
+    log_prob = model.prior.log_prob(z) - log_det
+    return -torch.mean(potential.log_prob(x)) + torch.mean(log_prob)
+
+
+def forward_kl(model, potential, nsamples):
+    """setup.py:96-100 (KL): target samples scored by the flow."""
+    x = potential.sample(nsamples, flatten=True)
+    z, prior_logprob, log_det = model(x)
+    logprob = prior_logprob + log_det
+    return -torch.mean(logprob) + torch.mean(potential.log_prob(x))
+
+
+def generate_from_nf(model, nsamples=50, batchsize=50):
+    """test.py:13-22: nsamples // batchsize batches of model.sample."""
+    xs, lps = [], []
+    for _ in range(nsamples // batchsize):
+        x, log_px, _ = model.sample(batchsize)
+        xs.append(x)
+        lps.append(log_px)
+    return torch.cat(xs, dim=0), torch.cat(lps, dim=0)
+
+
+def evaluate(model, x, batchsize=50):
+    """test.py:24-31: model.evaluate over len(x) // batchsize batches."""
+    return torch.cat([model.evaluate(x[i * batchsize:(i + 1) * batchsize])
+                      for i in range(len(x) // batchsize)], dim=0)
+
+
+def q_matrix(cfg, model, potential, nsamples, batchsize=500):
+    """The [2, nsamples, 2] tensor Q of test.py:34-50 without relaxation:
+    Q[0] = (log q, -U/kT) of flow samples, Q[1] = the same of target samples.
+    The energies stay on the device; nothing is written and no solver runs."""
+    d = cfg.dataset
+    traj0, q00 = generate_from_nf(model, nsamples, batchsize=batchsize)
+    q01 = -(potential.potential(traj0.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(q00.device)
+    Q0 = torch.transpose(torch.vstack((q00, q01)), 0, 1)
+    traj1 = potential.sample(nsamples)
+    traj1 = traj1.reshape(len(traj1), -1).to(q00.device)
+    q10 = torch.zeros(nsamples, device=q00.device)
+    q10 += evaluate(model, traj1, batchsize=batchsize)
+    q11 = -(potential.potential(traj1.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(q00.device)
+    Q1 = torch.transpose(torch.vstack((q10, q11)), 0, 1)
+    return torch.stack((Q0, Q1))

@@ -162,7 +162,9 @@ class GraphedSample(_Graphed):
 
     def __init__(self, model, n_samples, warmup=2):
         self.n = int(n_samples)
-        super().__init__(lambda: model.sample(self.n), model.prior.loc.device, warmup, model=model)
+        prior = model.prior  # the Normal prior's loc, or a systems prior's centers
+        where = prior.loc if hasattr(prior, "loc") else prior.centers
+        super().__init__(lambda: model.sample(self.n), where.device, warmup, model=model)
 
     def __call__(self):
         return self.replay()

@@ -462,6 +462,104 @@ def normal_logprob(z, out, *, scale=1.0, hld=0.0, logdet=None, sign=1, status=No
               float(scale), float(hld), int(sign), _vec(status, 1, "status", torch.int32), _stream(dev))
 
 
+# ---------------------------------------------------------------------------
+# priors and targets of the applications layer (nfk_systems.hip)
+def _box(boxlength):
+    return (0, 0.0) if boxlength is None else (1, float(boxlength))
+
+
+def einstein_logprob(z, centers, out, *, scale, hld, boxlength=None, logdet=None, sign=1, status=None):
+    """nfk_einstein_logprob.  centers: dense fp32 [natoms, dim]; ``hld`` is the
+    per-atom half_log_det; ``boxlength`` None skips the wrap."""
+    dev = _require_hip(z, centers, out, logdet, status)
+    natoms, dim = centers.shape
+    B = z.shape[0]
+    zp, ldz = _mat(z, "z")
+    if z.shape[1] != natoms * dim:
+        raise ValueError("z must be [B, %d], got %s" % (natoms * dim, tuple(z.shape)))
+    has_box, L = _box(boxlength)
+    _timed("nfk_einstein_logprob", dev, "nfk_einstein_logprob", zp, ldz,
+           _vec(centers, natoms * dim, "centers"), _vec(logdet, B, "logdet"), _vec(out, B, "out"), B,
+           natoms, dim, float(scale), float(hld), has_box, L, int(sign),
+           _vec(status, 1, "status", torch.int32), _stream(dev))
+
+
+def einstein_logprob_bwd(z, centers, g, gz, *, scale, boxlength=None):
+    dev = _require_hip(z, centers, g, gz)
+    natoms, dim = centers.shape
+    B = z.shape[0]
+    zp, ldz = _mat(z, "z")
+    gp, ldg = _mat(gz, "gz")
+    if z.shape[1] != natoms * dim or gz.shape != z.shape:
+        raise ValueError("z and gz must be [B, %d]" % (natoms * dim))
+    has_box, L = _box(boxlength)
+    _timed("nfk_einstein_logprob_bwd", dev, "nfk_einstein_logprob_bwd", zp, ldz,
+           _vec(centers, natoms * dim, "centers"), _vec(g, B, "g"), gp, ldg, B, natoms, dim,
+           float(scale), has_box, L, _stream(dev))
+
+
+def gmix_supported(ncenters, dim):
+    return bool(_lib.load().nfk_gmix_supported(ncenters, dim))
+
+
+def gmix_logprob(x, centers, scales, hlds, out, *, npart, logdet=None, sign=1, status=None):
+    """nfk_gmix_logprob.  centers [M, dim], scales [M], hlds [M] dense fp32."""
+    dev = _require_hip(x, centers, scales, hlds, out, logdet, status)
+    M, dim = centers.shape
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    if x.shape[1] != npart * dim:
+        raise ValueError("x must be [B, %d], got %s" % (npart * dim, tuple(x.shape)))
+    _timed("nfk_gmix_logprob", dev, "nfk_gmix_logprob", xp, ldx, _vec(centers, M * dim, "centers"),
+           _vec(scales, M, "scales"), _vec(hlds, M, "hlds"), _vec(logdet, B, "logdet"),
+           _vec(out, B, "out"), B, int(npart), dim, M, int(sign),
+           _vec(status, 1, "status", torch.int32), _stream(dev))
+
+
+def gmix_logprob_bwd(x, centers, scales, hlds, g, gx, *, npart):
+    dev = _require_hip(x, centers, scales, hlds, g, gx)
+    M, dim = centers.shape
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    gp, ldg = _mat(gx, "gx")
+    if x.shape[1] != npart * dim or gx.shape != x.shape:
+        raise ValueError("x and gx must be [B, %d]" % (npart * dim))
+    _timed("nfk_gmix_logprob_bwd", dev, "nfk_gmix_logprob_bwd", xp, ldx,
+           _vec(centers, M * dim, "centers"), _vec(scales, M, "scales"), _vec(hlds, M, "hlds"),
+           _vec(g, B, "g"), gp, ldg, B, int(npart), dim, M, _stream(dev))
+
+
+def lj_supported(n, dim):
+    return bool(_lib.load().nfk_lj_supported(n, dim))
+
+
+def _lj_consts(boxlength, sigma, epsilon, cutoff, shift):
+    return (float(boxlength), float(sigma), float(epsilon), 0 if cutoff is None else 1,
+            0.0 if cutoff is None else float(cutoff), 1 if shift else 0)
+
+
+def lj_potential(x, out, *, n, dim, boxlength, sigma=1.0, epsilon=1.0, cutoff=None, shift=True):
+    """nfk_lj_potential.  x: [B, n*dim] rows of n particles."""
+    dev = _require_hip(x, out)
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    if x.shape[1] != n * dim:
+        raise ValueError("x must be [B, %d], got %s" % (n * dim, tuple(x.shape)))
+    _timed("nfk_lj_potential", dev, "nfk_lj_potential", xp, ldx, _vec(out, B, "out"), B, n, dim,
+           *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
+
+
+def lj_potential_bwd(x, g, gx, *, n, dim, boxlength, sigma=1.0, epsilon=1.0, cutoff=None, shift=True):
+    dev = _require_hip(x, g, gx)
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    gp, ldg = _mat(gx, "gx")
+    if x.shape[1] != n * dim or gx.shape != x.shape:
+        raise ValueError("x and gx must be [B, %d]" % (n * dim))
+    _timed("nfk_lj_potential_bwd", dev, "nfk_lj_potential_bwd", xp, ldx, _vec(g, B, "g"), gp, ldg, B,
+           n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
+
+
 def trig_features(x, feat, B):
     dev = _require_hip(x, feat)
     n_rows, n = x.shape

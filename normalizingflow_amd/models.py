@@ -11,7 +11,9 @@ accumulating log|det| in place (no per-layer temporaries, no host syncs); the
 reference's errors are raised after the chain from the kernels' status words
 (config.STRICT_CHECKS).  An isotropic-normal prior (the reference's "Normal"
 prior, applications/src/setup.py:25-30) is evaluated by the fused
-nfk_normal_logprob epilogue; any other prior object is called as is.
+nfk_normal_logprob epilogue, a systems.EinsteinCrystal or
+systems.GaussianMixture prior by its own kernel in the same place (log|det|
+fused, one status word); any other prior object is called as is.
 """
 from __future__ import annotations
 
@@ -22,10 +24,14 @@ import torch.nn as nn
 
 from . import config
 from . import kernels as K_
+from . import systems as S_
 from .flows import NSF_CL, RealNVP, _HipFlow, _check_input, _invalidate_after_load, _needs_grad, check_status
 from .flows import rnvp_pad, rnvp_unpad
 
 __all__ = ["NormalizingFlowModel", "NormalizingFlow"]
+
+
+_SYSTEM_PRIORS = (S_.EinsteinCrystal, S_.GaussianMixture)
 
 
 def _iso_normal(prior):
@@ -195,8 +201,12 @@ class NormalizingFlowModel(nn.Module):
     # ------------------------------------------------------------------ prior
     def _prior_consts(self):
         p = self.prior
-        key = (id(p),) + tuple((t.data_ptr(), t._version) for t in (p.loc, p.scale_tril)) \
-            if isinstance(p, torch.distributions.MultivariateNormal) else (id(p),)
+        if isinstance(p, torch.distributions.MultivariateNormal):
+            key = (id(p),) + tuple((t.data_ptr(), t._version) for t in (p.loc, p.scale_tril))
+        elif isinstance(p, _SYSTEM_PRIORS):  # never the isotropic Normal: the key covers their tensors
+            key = (id(p),) + p._cache_key()
+        else:
+            key = (id(p),)
         if key != self._prior_key:
             self._prior_iso = _iso_normal(p)
             self._prior_key = key
@@ -208,7 +218,12 @@ class NormalizingFlowModel(nn.Module):
         turns into the ValueError of torch's argument validation; any other
         prior is called as is and validates by itself."""
         iso = self._prior_consts()
-        if iso is not None and z.shape[1] == self.prior.loc.shape[0]:
+        if isinstance(self.prior, _SYSTEM_PRIORS):
+            # fp32 tensors on z's device and the prior's width: its kernel with the
+            # log|det| fused (an autograd node under training); else its torch path
+            if z.shape[1] == self.prior.width and self.prior._kernel_ok(z):
+                return self.prior._fused(z, logdet, sign, status)
+        elif iso is not None and z.shape[1] == self.prior.loc.shape[0]:
             if not (torch.is_grad_enabled() and z.requires_grad):
                 out = torch.empty(z.shape[0], dtype=torch.float32, device=z.device)
                 K_.normal_logprob(z, out, scale=iso[0], hld=iso[1], logdet=logdet, sign=sign,

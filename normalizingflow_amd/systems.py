@@ -1,0 +1,466 @@
+"""Priors and targets of the reference's applications layer
+(applications/src/systems.py): EinsteinCrystal, GaussianMixture and LJ, with
+the reference's constructor signatures and method names.
+
+fp32 tensors on the HIP device take the kernels of nfk_systems.hip (one launch
+per log_prob / potential, one per backward; no [B, N, N] temporary for LJ).
+Every other input -- CPU tensors, other float dtypes, parameters that require
+grad, shapes the kernels do not take -- runs the plain-torch restatement in
+this module: the same formulas in the input's dtype, differentiable by
+autograd.  (Unlike the flow layers, which refuse CPU tensors, these classes
+are plain formulas and serve as their own CPU companions.)
+
+As priors of ``NormalizingFlowModel`` the Einstein crystal and the mixture get
+what the Normal prior gets: the kernel with ``+ sign * log|det|`` fused, a
+status word for the reference's NaN ``ValueError``, an autograd node under
+training and HIP-graph capture (models._prior_log_prob).
+
+Out of scope: LAMMPS, Fe, the MD integrators (integration_step,
+set_position, ...), HMC, the MBAR/BAR solvers and plotting.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import kernels as K_
+from .flows import check_status
+
+__all__ = ["EinsteinCrystal", "GaussianMixture", "LJ", "read_xyz", "load_position"]
+
+_LOG_2PI = math.log(2 * math.pi)
+
+
+# ---------------------------------------------------------------------------
+# files
+def read_xyz(path):
+    """Frames of an XYZ file in the format utils.write_coord emits (a count
+    line, a comment line, then ``type x y z`` lines) as a float32 tensor
+    [nframes, natoms, 3]."""
+    with open(path) as f:
+        lines = f.read().splitlines()
+    frames, i = [], 0
+    while i < len(lines):
+        if not lines[i].strip():
+            i += 1
+            continue
+        n = int(lines[i].split()[0])
+        rows = lines[i + 2:i + 2 + n]
+        if len(rows) != n:
+            raise ValueError("%s: frame %d is truncated (%d of %d atoms)" % (path, len(frames), len(rows), n))
+        frames.append([[float(v) for v in r.split()[1:4]] for r in rows])
+        i += n + 2
+    if not frames:
+        raise ValueError("%s: no frames" % path)
+    if any(len(fr) != len(frames[0]) for fr in frames):
+        raise ValueError("%s: frames with different atom counts" % path)
+    return torch.tensor(np.asarray(frames, dtype=np.float32))
+
+
+def load_position(path):
+    """utils.load_position: the frames of an XYZ file, [nframes, natoms * 3]."""
+    return read_xyz(path).flatten(start_dim=1)
+
+
+def _load_traj(src):
+    if torch.is_tensor(src):
+        return src.float()
+    if isinstance(src, str):
+        if src.endswith(".npy"):
+            return torch.from_numpy(np.load(src, allow_pickle=False)).float()
+        if src.endswith(".pt"):
+            return torch.as_tensor(torch.load(src, map_location="cpu", weights_only=True)).float()
+        return read_xyz(src)
+    return torch.as_tensor(np.asarray(src)).float()
+
+
+def _centers(centers, dim, device):
+    if isinstance(centers, str):
+        return load_position(centers).reshape(-1, dim).to(device)
+    if torch.is_tensor(centers):
+        return centers.float().to(device)
+    return torch.tensor(centers).float().to(device)
+
+
+def _wrap(v, boxlength):
+    """The reference's single wrap: v - (|v| > 0.5 L) sign(v) L."""
+    return v - (torch.abs(v) > 0.5 * boxlength) * torch.sign(v) * boxlength
+
+
+def _rows(x, width):
+    """x as [B, width] rows with unit column stride (a view when it already is)."""
+    z = x.reshape(-1, width)
+    return z if z.shape[1] <= 1 or z.stride(1) == 1 else z.contiguous()
+
+
+def _raise_nan(x, who):
+    if bool((x != x).any()):
+        raise ValueError("Expected value argument to be within the support (IndependentConstraint("
+                         "Real(), 1)) of the distribution %s, but found invalid values (NaN)"
+                         % type(who).__name__)
+
+
+class _KernelBacked:
+    """Shared dispatch: ``use_kernels = False`` on an object forces its torch path."""
+
+    use_kernels = True
+    _validate_args = True  # the components are MultivariateNormals with torch's default validation
+
+    def _on_device(self, x, *params):
+        return (self.use_kernels and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and all(p.device == x.device and p.dtype == torch.float32 and not p.requires_grad
+                        for p in params))
+
+    def _fused(self, z, logdet, sign, status):
+        """log_prob(z) + sign * logdet by the kernel; z: [B, width] fp32 on the device."""
+        z = _rows(z, self.width)
+        if torch.is_grad_enabled() and z.requires_grad:
+            lp = self._fn.apply(z, self, status)
+            return lp if logdet is None else (lp + logdet if sign >= 0 else lp - logdet)
+        out = torch.empty(z.shape[0], dtype=torch.float32, device=z.device)
+        self._launch(z.detach(), out, logdet, sign, status)
+        return out
+
+    def log_prob(self, x):
+        if self._kernel_ok(x):
+            status = torch.zeros(1, dtype=torch.int32, device=x.device)
+            out = self._fused(x, None, 1, status)
+            check_status(status, 0, prior=self)  # a NaN row: torch's ValueError (config.STRICT_CHECKS)
+            return out
+        return self._log_prob_torch(x)
+
+    def potential(self, x):
+        return -self.log_prob(x)
+
+    def get_force(self, x):
+        x.requires_grad_()
+        pot = self.potential(x)
+        return -torch.autograd.grad(pot, x, torch.ones_like(pot), create_graph=True)[0]
+
+
+# ---------------------------------------------------------------------------
+class _EinsteinFn(torch.autograd.Function):
+    """nfk_einstein_logprob, differentiable in z: gz = -alpha dev_wrapped g."""
+
+    @staticmethod
+    def forward(ctx, z, prior, status):
+        out = torch.empty(z.shape[0], dtype=torch.float32, device=z.device)
+        prior._launch(z, out, None, 1, status)
+        ctx.save_for_backward(z)
+        ctx.prior = prior
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        z, = ctx.saved_tensors
+        p = ctx.prior
+        gz = torch.empty(z.shape, dtype=torch.float32, device=z.device)
+        K_.einstein_logprob_bwd(z, p.centers, g.contiguous(), gz, scale=p._consts()[0], boxlength=p.boxlength)
+        return gz, None, None
+
+
+class EinsteinCrystal(_KernelBacked):
+    """systems.py:340-375: independent N(centre_i, I/alpha) per atom, with one
+    minimum-image wrap of the deviation when ``boxlength`` is not None (0 is
+    legal and wraps nothing)."""
+
+    _fn = _EinsteinFn
+
+    def __init__(self, centers, dim=3, boxlength=None, alpha=50, device="cpu"):
+        self.device = device
+        self.centers = _centers(centers, dim, device)
+        self.natoms = self.centers.shape[0]
+        self.alpha = alpha
+        self.dim = dim
+        self.boxlength = boxlength
+        self._ck = None
+
+    @property
+    def width(self):
+        return self.natoms * self.dim
+
+    def _norm_consts(self, dtype):
+        """(scale_tril diagonal, half_log_det) of MultivariateNormal(0, I/alpha)
+        as torch evaluates them in ``dtype`` (CPU scalars: no device sync)."""
+        scale = (1 / self.alpha * torch.ones((), dtype=dtype)).sqrt()
+        return scale, scale.log().expand(self.dim).sum()
+
+    def _consts(self):
+        key = (self.alpha, self.dim)
+        if self._ck is None or self._ck[0] != key:
+            s, h = self._norm_consts(torch.float32)
+            self._ck = (key, (float(s), float(h)))
+        return self._ck[1]
+
+    def _cache_key(self):
+        c = self.centers
+        return (c.data_ptr(), c._version, self.alpha, self.dim, self.boxlength)
+
+    def _kernel_ok(self, x):
+        return (self._on_device(x, self.centers) and self.centers.shape == (self.natoms, self.dim)
+                and self.centers.is_contiguous() and x.numel() % self.width == 0)
+
+    def _launch(self, z, out, logdet, sign, status):
+        scale, hld = self._consts()
+        K_.einstein_logprob(z, self.centers, out, scale=scale, hld=hld, boxlength=self.boxlength,
+                            logdet=logdet, sign=sign, status=status)
+
+    def _log_prob_torch(self, x):
+        if self._validate_args:
+            _raise_nan(x, self)
+        c = self.centers if self.centers.dtype == x.dtype else self.centers.to(x.dtype)
+        dev = x.reshape(-1, self.natoms, self.dim) - c
+        if self.boxlength is not None:
+            dev = _wrap(dev, self.boxlength)
+        scale, hld = self._norm_consts(x.dtype)
+        y = dev / scale.to(x.device)
+        lp = -0.5 * (self.dim * _LOG_2PI + (y * y).sum(-1)) - hld.to(x.device)
+        return torch.sum(lp, dim=1)
+
+    def sample(self, nsamples, flatten=True):
+        with torch.no_grad():
+            if isinstance(nsamples, tuple):
+                nsamples = nsamples[0]
+            c = self.centers
+            noise = torch.randn(nsamples, self.natoms, self.dim, dtype=c.dtype, device=c.device)
+            samples = c + noise * float(self._norm_consts(torch.float32)[0])
+            if self.boxlength is not None:
+                samples = _wrap(samples, self.boxlength)
+            return samples.reshape(nsamples, -1) if flatten else samples
+
+
+# ---------------------------------------------------------------------------
+class _GmixFn(torch.autograd.Function):
+    """nfk_gmix_logprob, differentiable in x: sum_i w_i (-(x - c_i)/var_i) g."""
+
+    @staticmethod
+    def forward(ctx, x, prior, status):
+        out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        prior._launch(x, out, None, 1, status)
+        ctx.save_for_backward(x)
+        ctx.prior = prior
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        p = ctx.prior
+        scales, hlds = p._consts()
+        gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        K_.gmix_logprob_bwd(x, p.centers, scales, hlds, g.contiguous(), gx, npart=p.nparticles)
+        return gx, None, None
+
+
+class GaussianMixture(_KernelBacked):
+    """systems.py:257-311: ``nparticles`` independent particles, each drawn from
+    an equal-weight mixture of N(centre_i, var_i I).  log_prob keeps the
+    reference's arithmetic, sum_i (1/M) exp(log N_i(x)) in centre order and
+    then log: not a log-sum-exp, so a particle far from every centre gives
+    -inf.  ``sample`` draws the components with torch.randint on the device."""
+
+    _fn = _GmixFn
+
+    def __init__(self, centers, vars, npoints=None, dim=3, device="cpu"):
+        self.dim = dim
+        self.device = device
+        self.centers = _centers(centers, dim, device)
+        self.ncenters = len(self.centers)
+        self.vars = (vars.float() if torch.is_tensor(vars) else torch.tensor(vars).float()).to(device)
+        if self.vars.dim() == 0:
+            self.vars = self.vars.expand(self.ncenters)
+        elif self.vars.numel() == self.ncenters:  # [[v]] per centre (Gaussian_rnvp.yaml): v I all the same
+            self.vars = self.vars.reshape(self.ncenters)
+        else:
+            raise ValueError("vars must be a scalar or one variance per centre, got shape %s"
+                             % (tuple(self.vars.shape),))
+        self.nparticles = self.ncenters if npoints is None else npoints
+        self._ck = None
+
+    @property
+    def width(self):
+        return self.nparticles * self.dim
+
+    def _norm_consts(self, dtype):
+        """Per-centre (scale_tril diagonal, half_log_det) as torch evaluates
+        them for MultivariateNormal(c_i, var_i I) in ``dtype``."""
+        scales = self.vars.to(dtype).sqrt()
+        return scales, scales.log().unsqueeze(1).expand(self.ncenters, self.dim).sum(1)
+
+    def _cache_key(self):
+        c, v = self.centers, self.vars
+        return (c.data_ptr(), c._version, v.data_ptr(), v._version, self.nparticles, self.dim)
+
+    def _consts(self):
+        key = self._cache_key()
+        if self._ck is None or self._ck[0] != key:
+            with torch.no_grad():
+                s, h = self._norm_consts(torch.float32)
+                self._ck = (key, (s.contiguous(), h.contiguous()))
+        return self._ck[1]
+
+    def _kernel_ok(self, x):
+        return (self._on_device(x, self.centers, self.vars) and K_.gmix_supported(self.ncenters, self.dim)
+                and self.centers.shape == (self.ncenters, self.dim) and self.centers.is_contiguous()
+                and x.numel() % self.width == 0)
+
+    def _launch(self, x, out, logdet, sign, status):
+        scales, hlds = self._consts()
+        K_.gmix_logprob(x, self.centers, scales, hlds, out, npart=self.nparticles, logdet=logdet,
+                        sign=sign, status=status)
+
+    def _log_prob_torch(self, x):
+        if self._validate_args:
+            _raise_nan(x, self)
+        c = self.centers if self.centers.dtype == x.dtype else self.centers.to(x.dtype)
+        scales, hlds = self._norm_consts(x.dtype)
+        x = x.reshape(-1, self.dim)
+        prob = 0
+        for i in range(self.ncenters):
+            y = (x - c[i]) / scales[i]
+            lp = -0.5 * (self.dim * _LOG_2PI + (y * y).sum(-1)) - hlds[i]
+            prob = prob + 1 / self.ncenters * torch.exp(lp)
+        return torch.sum(torch.log(prob).reshape(-1, self.nparticles), dim=1)
+
+    def get_potential(self, x):
+        return self.potential(x)
+
+    def force(self, x):
+        return self.get_force(x)
+
+    def sample(self, nsamples, flatten=True):
+        with torch.no_grad():
+            if isinstance(nsamples, tuple):
+                nsamples = nsamples[0]
+            c = self.centers
+            n = nsamples * self.nparticles
+            which = torch.randint(self.ncenters, (n,), device=c.device)
+            scales = self._norm_consts(torch.float32)[0]
+            noise = torch.randn(n, self.dim, dtype=c.dtype, device=c.device)
+            samples = c.index_select(0, which) + noise * scales.index_select(0, which).unsqueeze(1)
+            if flatten:
+                return samples.reshape(nsamples, -1)
+            return samples.reshape(nsamples, self.nparticles, self.dim)
+
+
+# ---------------------------------------------------------------------------
+class _LJFn(torch.autograd.Function):
+    """nfk_lj_potential on [B, n*dim] rows, differentiable in x."""
+
+    @staticmethod
+    def forward(ctx, x, lj, n, dim):
+        out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        K_.lj_potential(x, out, n=n, dim=dim, **lj._kw())
+        ctx.save_for_backward(x)
+        ctx.lj, ctx.n, ctx.d = lj, n, dim
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        K_.lj_potential_bwd(x, g.contiguous(), gx, n=ctx.n, dim=ctx.d, **ctx.lj._kw())
+        return gx, None, None, None
+
+
+class LJ:
+    """systems.py:144-189: Lennard-Jones particles in a periodic cubic box,
+    plus the trajectory holder of SimData (``sample``).  ``pos_dir`` may be a
+    tensor, a ``.npy`` / ``.pt`` path or an XYZ file.
+
+    ``potential`` keeps the reference's arithmetic: one minimum-image wrap per
+    component of the pair vector, ``d + (d == 0)``, ``1/d`` zeroed beyond the
+    cutoff, the ``- s6^2 + s6`` shift (s6 = (sigma/cutoff)^6), the final
+    ``* inv * d`` factor (zero on the diagonal, for coincident pairs and
+    beyond the cutoff) and ``sum / 2``.  ``boxlength=None`` raises TypeError
+    as the reference's ``0.5 * None`` does.
+
+    ``force`` is -grad potential (the backward kernel on the device, autograd
+    elsewhere).  This is the working form: the reference's ``force`` stops at
+    a NameError (``force_mag``, systems.py:220)."""
+
+    use_kernels = True
+    _CHUNK_ELEMS = 1 << 24  # pair components per chunk of the torch path
+
+    def __init__(self, pos_dir=None, boxlength=None, device="cpu", epsilon=1., sigma=1., cutoff=None,
+                 shift=True):
+        self.device = device
+        if pos_dir is not None:
+            self.traj = _load_traj(pos_dir).to(device)
+        self.epsilon = epsilon
+        self.sigma = sigma
+        self.cutoff = cutoff
+        self.shift = shift
+        self.boxlength = boxlength
+
+    def _kw(self):
+        return dict(boxlength=self.boxlength, sigma=self.sigma, epsilon=self.epsilon, cutoff=self.cutoff,
+                    shift=self.shift)
+
+    def _kernel_ok(self, pos):
+        return (self.use_kernels and torch.is_tensor(pos) and pos.is_cuda and pos.dtype == torch.float32
+                and pos.dim() >= 2 and K_.lj_supported(pos.shape[-2], pos.shape[-1]))
+
+    def potential(self, particle_pos):
+        half = 0.5 * self.boxlength  # None: the reference's TypeError
+        if self._kernel_ok(particle_pos):
+            n, dim = particle_pos.shape[-2:]
+            x = _rows(particle_pos, n * dim)
+            if torch.is_grad_enabled() and x.requires_grad:
+                out = _LJFn.apply(x, self, n, dim)
+            else:
+                out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+                K_.lj_potential(x.detach(), out, n=n, dim=dim, **self._kw())
+            return out.reshape(particle_pos.shape[:-2])
+        n, dim = particle_pos.shape[-2:]
+        rows = max(1, self._CHUNK_ELEMS // max(1, n * n * dim))
+        if particle_pos.dim() < 3 or particle_pos.shape[:-2].numel() <= rows:
+            return self._potential_torch(particle_pos, half)
+        flat = particle_pos.reshape(-1, n, dim)  # row chunks: no [B, N, N, dim] temporary of the whole batch
+        out = torch.cat([self._potential_torch(flat[i:i + rows], half) for i in range(0, flat.shape[0], rows)])
+        return out.reshape(particle_pos.shape[:-2])
+
+    def _potential_torch(self, particle_pos, half):
+        pair_dist = particle_pos.unsqueeze(-2) - particle_pos.unsqueeze(-3)
+        pair_dist = pair_dist - (torch.abs(pair_dist) > half) * torch.sign(pair_dist) * self.boxlength
+        distances = torch.linalg.norm(pair_dist, axis=-1)
+        scaled_distances = distances + (distances == 0)
+        distances_inverse = 1 / scaled_distances
+        if self.cutoff is not None:
+            distances_inverse = distances_inverse - (distances > self.cutoff) * distances_inverse
+        pow_6 = torch.pow(self.sigma * distances_inverse, 6)
+        if self.cutoff is not None and self.shift:
+            pow_6_shift = (self.sigma / self.cutoff) ** 6
+            pair_potential = self.epsilon * 4 * (torch.pow(pow_6, 2) - pow_6 - pow_6_shift ** 2 + pow_6_shift)
+        else:
+            pair_potential = self.epsilon * 4 * (torch.pow(pow_6, 2) - pow_6)
+        pair_potential = pair_potential * distances_inverse * distances
+        return torch.sum(pair_potential, axis=(-1, -2)) / 2
+
+    def force(self, particle_pos):
+        if self._kernel_ok(particle_pos):
+            if self.boxlength is None:
+                raise TypeError("unsupported operand type(s) for *: 'float' and 'NoneType' (boxlength=None)")
+            n, dim = particle_pos.shape[-2:]
+            x = _rows(particle_pos.detach(), n * dim)
+            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            K_.lj_potential_bwd(x, torch.ones(x.shape[0], dtype=torch.float32, device=x.device), gx, n=n,
+                                dim=dim, **self._kw())
+            return -gx.reshape(particle_pos.shape)
+        with torch.enable_grad():
+            x = particle_pos.detach().requires_grad_()
+            pot = self.potential(x)
+            return -torch.autograd.grad(pot, x, torch.ones_like(pot))[0]
+
+    def sample(self, nsamples, flatten=True, random=True):
+        if random:
+            idx = torch.randint(len(self.traj), [nsamples]).to(self.traj.device)
+            samples = self.traj.index_select(0, idx)
+        else:
+            samples = self.traj[:nsamples]
+        return samples.reshape(nsamples, -1) if flatten else samples
