@@ -102,6 +102,8 @@ __device__ __forceinline__ void gemm_h2(const h8 (&bh)[kC2Tiles][KBH], const h8 
     }
 }
 
+// GEMM over the parts J, J + 1, ... of an NT-tile record; each part is followed
+// by step(J, last), both compile-time constants (std::integral_constant)
 template <int KBH, bool T1, int NT, int NS, int J, class Step>
 __device__ __forceinline__ void gemm_parts2(const h8 (&bh)[kC2Tiles][KBH], const h8 (&bl)[kC2Tiles][KBH],
                                             const h4 (&btail)[kC2Tiles], const float4* slot, int lane,
@@ -110,9 +112,62 @@ __device__ __forceinline__ void gemm_parts2(const h8 (&bh)[kC2Tiles][KBH], const
     constexpr int N = (NT - T0) < NS ? (NT - T0) : NS;
     constexpr bool last = T0 + NS >= NT;
     gemm_h2<KBH, T1, N, NS, T0, NT>(bh, bl, btail, slot, lane, acc);
-    step(last);
+    step(std::integral_constant<int, J>{}, std::integral_constant<bool, last>{});
     if constexpr (!last) gemm_parts2<KBH, T1, NT, NS, J + 1>(bh, bl, btail, slot, lane, acc, step);
 }
+
+// ---- compile-time weight staging.  The chain knows at compile time which
+// sub-record follows every GEMM part, so the copy of the next one is a
+// constant function of the wave number instead of stage_tiles' block loop:
+// with NS = 4 tiles and 4 waves, wave w copies tile T0 + w's KBH x {hi, lo}
+// blocks, waves 0 .. ceil(nts / 2) - 1 the live tail blocks, the last wave
+// the record's bias block.  Every block lands where stage_tiles puts it
+// (subrec_tile_src is the layout); which wave carries it is free, the
+// barrier orders the reads.
+
+// a tile's hi and lo block: adjacent in the pack and in the slot, so one m0
+// write serves both -- the instruction offset of an LDS-DMA load moves the
+// source and the LDS destination alike.  m0 = lds + LOFF.
+template <int LOFF>
+__device__ __forceinline__ void dma16x2(const float* gsrc, uint32_t lds) {
+    uint32_t saved;  // m0 is reserved by the compiler: restore it
+    asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %1, %3\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %2, off\n\t"
+                 "global_load_lds_dwordx4 %2, off offset:1024\n\ts_mov_b32 m0, %0"
+                 : "=&s"(saved)
+                 : "s"(lds), "v"(gsrc), "i"(LOFF)
+                 : "memory", "scc");
+}
+
+// Tiles [T0, T0 + NS) of an NT-tile record (BIAS: and its bias block, which
+// every part of the record reads at the same slot address -- gemm_h2's
+// bias[(T0 + t) 4 + q] -- so only part 0 carries it).
+template <int KBH, bool T1, int NS, int NT, int T0, bool BIAS>
+struct SubCopy {
+    static_assert(NS == kNsfWaves, "one tile per wave");
+    static constexpr int NF = KBH * NS * 2, NTB = T1 ? (NS + 1) / 2 : 0;
+    static constexpr int nts = (NT - T0) < NS ? (NT - T0) : NS;
+    static constexpr int NTG = T1 ? (nts + 1) / 2 : 0;  // tail blocks holding a live tile
+    static constexpr int kTail = KBH * NT * 2 + (T0 >> 1), kBias = KBH * NT * 2 + (T1 ? (NT + 1) / 2 : 0);
+    // this lane's source of wave wid's first block (rec wave-uniform)
+    static __device__ __forceinline__ const float* lane_src(const float* rec, int wid, int lane) {
+        return rec + (int64_t)(T0 + wid) * 512 + lane * 4;
+    }
+    // k-blocks KB .. KBH - 1 of this wave's tile
+    template <int KB>
+    static __device__ __forceinline__ void tile_blocks(const float* g, uint32_t wbase) {
+        dma16x2<KB * NS * 2048>(g + KB * NT * 512, wbase);
+        if constexpr (KB + 1 < KBH) tile_blocks<KB + 1>(g, wbase);
+    }
+    // g = lane_src(rec, wid, lane), wbase = the slot's LDS address + 2048 wid
+    static __device__ __forceinline__ void issue(const float* g, uint32_t wbase, int wid) {
+        if (nts == NS || wid < nts) tile_blocks<0>(g, wbase);
+        if (NTG > 0 && wid < NTG)  // tail block wid: g is (T0 + wid) 512 floats into the record
+            dma16(g + (kTail * 256 - T0 * 512) - wid * 256, wbase + NF * 1024 - wid * 1024);
+        if (BIAS && wid == NS - 1)
+            dma16(g + (kBias * 256 - (T0 + NS - 1) * 512), wbase + (NF + NTB) * 1024 - (NS - 1) * 2048);
+    }
+};
 
 // LDS of one workgroup: the sub-record slot, the status words and byte maps,
 // each wave's kC2Tiles x [16][D + 1] row tiles, each wave's kC2Tiles bin
@@ -176,18 +231,45 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
 #pragma unroll
     for (int s = 0; s < NTL; ++s) btail[s] = h4{0, 0, 0, 0};
 
-    const int NSR = 1 + SP::NH2 + A->NCH * SP::SPC;
-    int sr = 0;
-    auto gemm_end = [&](bool last) {
+    // The sub-record stream of a layer (NfkSplit): layer 1, the parts of layer
+    // 2, then per chunk the parts of the first logits record (offA), of the
+    // second (offB) and of the derivative record (offC).  gemm_end<RK, J, last>
+    // ends part J of a record of kind RK: barrier (every wave's reads of the
+    // slot returned), the copy of the sub-record that follows -- known at
+    // compile time except after a derivative record's last part (the next
+    // chunk, or the next layer's layer 1) -- and, between the parts of one
+    // record, the wait for it and a second barrier.  The source address is
+    // formed before the first barrier: between the two barriers stand the
+    // copies alone.
+    constexpr int kRecH1 = 0, kRecH2 = 1, kRecA = 2, kRecB = 3, kRecD = 4;
+    constexpr int NS = SP::NS;
+    static_assert(K > 1, "the derivative record has K - 1 tiles");
+    const uint32_t wbase = lds_addr(slot) + wid * 2048;
+    const float* pkn = pk;  // the next layer's pack (the layer's last copy)
+    const float* wc = pk;   // the current chunk's records
+    int ch = 0;
+    auto gemm_end = [&](auto rk, auto jc, auto lastc) {
+        constexpr int RK = decltype(rk)::value, J = decltype(jc)::value;
+        constexpr bool last = decltype(lastc)::value;
+        constexpr bool same = RK != kRecH1 && !last;      // next: part J + 1 of this record
+        constexpr bool fork = RK == kRecD && last;        // next: the run-time choice
+        constexpr int NK = same ? RK : (fork ? kRecA : RK + 1);
+        constexpr int NNT = NK == kRecH2 ? HT : (NK == kRecD ? K - 1 : K);
+        using Next = SubCopy<KBH, T1, NS, NNT, same ? (J + 1) * NS : 0, !same>;
+        const bool more = !fork || ch + 1 < A->NCH;
+        const float* rec = NK == kRecH2 ? pk + A->o_h2
+                                        : (fork ? wc + (int64_t)A->blk_chunk * 256 : wc) +
+                                              (NK == kRecA ? offA : (NK == kRecB ? offB : offC)) * 256;
+        const float* g = Next::lane_src(rec, wid, lane);
+        asm volatile("" : "+v"(g));  // formed here, not between the barriers
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (sr + 1 < NSR) {
-            stage_split<KBH, T1, K, HT>(a, pk, sr + 1, offA, offB, offC, slot, wid, lane);
+        if (more) {
+            Next::issue(g, wbase, wid);
         } else if (lyr + 1 < NL) {
-            stage_split<KBH, T1, K, HT>(a, A->packs[lyr + 1], 0, offA, offB, offC, slot, wid, lane);
+            stage_record<kNsfWaves>(pkn + A->o_h1, A->blk_h1, slot, wid, lane);
         }
-        ++sr;
         if (!last) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -199,10 +281,16 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
-    auto gemm_rec = [&](auto& acc) {
+    auto gemm_rec = [&](auto rk, auto& acc) {
         constexpr int N = sizeof(acc[0]) / sizeof(f32x4);
-        gemm_parts2<KBH, T1, N, SP::NS, 0>(bh, bl, btail, slot, lane, acc, gemm_end);
+        gemm_parts2<KBH, T1, N, NS, 0>(bh, bl, btail, slot, lane, acc,
+                                       [&](auto jc, auto lastc) { gemm_end(rk, jc, lastc); });
     };
+    using RecH1 = std::integral_constant<int, kRecH1>;
+    using RecH2 = std::integral_constant<int, kRecH2>;
+    using RecA = std::integral_constant<int, kRecA>;
+    using RecB = std::integral_constant<int, kRecB>;
+    using RecD = std::integral_constant<int, kRecD>;
 
     // ---- prologue: the log|det| being accumulated (mode 2; a plain load
     // before any DMA is in flight), whole x rows of both tiles (rows past the
@@ -228,7 +316,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                 }
         }
     }
-    stage_split<KBH, T1, K, HT>(a, pk, 0, offA, offB, offC, slot, wid, lane);
+    stage_record<kNsfWaves>(pk + A->o_h1, A->blk_h1, slot, wid, lane);
     for (int i = threadIdx.x; i < (NL + 1) * D; i += 64 * kNsfWaves) cm[i] = (uint8_t)A->cmaps[i];
     if (saved)
         for (int i = threadIdx.x; i < (NL - 1) * D; i += 64 * kNsfWaves) cm[(NL + 1) * D + i] = (uint8_t)A->smaps[i];
@@ -239,9 +327,10 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
         asm volatile("" : "+s"(A));
         lyr = l;
         pk = A->packs[l];
+        pkn = A->packs[l + 1 < NL ? l + 1 : l];  // (the last layer reads no element past nlayers)
+        wc = pk + A->o_w3;
         c_lo = cm + l * D;
         c_up = c_lo + A->n_lo;
-        sr = 0;
         const FusedConst c = *(const FusedConst*)&A->c;  // by value: SGPRs for the layer
         const float un1 = pk[kHdrUnscale], un2 = pk[kHdrUnscale + 1], un3 = pk[kHdrUnscale + 2];
         bool any_in = false, any_nd = false;
@@ -317,14 +406,14 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                     h1[s][t] = mfma16(ahi, xh[s], h1[s][t]);
                 }
             }
-            gemm_end(true);
+            gemm_end(RecH1{}, std::integral_constant<int, 0>{}, std::true_type{});
 #pragma unroll
             for (int s = 0; s < NTL; ++s) act_operands<KBH, T1, HT>(h1[s], -2.0f * kL2E * unx[s], bh[s], bl[s], btail[s]);
         }
         epi_end();
         {
             f32x4 h2[NTL][HT];
-            gemm_rec(h2);
+            gemm_rec(RecH2{}, h2);
 #pragma unroll
             for (int s = 0; s < NTL; ++s) act_operands<KBH, T1, HT>(h2[s], -2.0f * kL2E * un2, bh[s], bl[s], btail[s]);
         }
@@ -336,11 +425,11 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
         float xv[NTL][4];
         int kb[NTL][4];
         float cw_k[NTL][4], w_k[NTL][4], ch_k[NTL][4], h_k[NTL][4];
-        for (int ch = 0; ch < A->NCH; ++ch) {
+        for (ch = 0; ch < A->NCH; ++ch, wc += (int64_t)A->blk_chunk * 256) {
             const int jbase = 16 * ch;
             {
                 f32x4 acc[NTL][K];
-                gemm_rec(acc);
+                gemm_rec(RecA{}, acc);
                 // map reads and x reads unconditional (a guarded read became a
                 // branch with its own LDS round trip per coordinate)
                 // (uniform) n_up a multiple of 16: every chunk's coordinates exist
@@ -366,7 +455,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
             epi_end();
             {
                 f32x4 acc[NTL][K];
-                gemm_rec(acc);
+                gemm_rec(RecB{}, acc);
 #pragma unroll
                 for (int s = 0; s < NTL; ++s)
                     knot_phase<K, false, 0, 4, true>(acc[s], xv[s], c, l2e3, kb[s], INV ? cw_k[s] : ch_k[s],
@@ -375,7 +464,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
             epi_end();
             {
                 f32x4 accd[NTL][DN];
-                gemm_rec(accd);
+                gemm_rec(RecD{}, accd);
 #pragma unroll
                 for (int s = 0; s < NTL; ++s) {
                     float* fs = reinterpret_cast<float*>(scr + s * K * 64);
