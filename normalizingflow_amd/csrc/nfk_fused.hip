@@ -207,7 +207,7 @@ bool wide_ok(int n_lo, int n_up, int H, int K) {
     if (n_lo < 1 || n_up < 1 || H < 1 || K < 2 || (K & 1)) return false;
     const Layout L = make_layout(n_lo, n_up, H, K, 1);
     if (L.T1 != 0 || L.KB1 > L.KBH || n_lo > 16 * ((L.NCH + 1) / 2)) return false;
-    if (kWideWGs * lds_alloc(wide_lds_bytes(n_lo, n_up)) > (size_t)kLdsBytes) return false;
+    if (lds_alloc(wide_lds_bytes(n_lo, n_up)) > (size_t)kLdsBytes) return false;
     bool kb = false, kk = false;
 #define CHK_KB(h) kb |= (L.KBH == h);
     NFK_WIDE_KB(CHK_KB)

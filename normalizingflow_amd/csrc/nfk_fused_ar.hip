@@ -56,28 +56,15 @@ using namespace nfk_fused;
 
 namespace {
 
-#ifndef NFK_AR_NS
-#define NFK_AR_NS 3
-#endif
-constexpr int kArNS = NFK_AR_NS;  // output tiles per sub-record (hidden widths up to 4 k-blocks)
+constexpr int kArNS = 3;  // output tiles per sub-record (hidden widths up to 4 k-blocks)
 // wider conditioners (the applications' H = 354: 11 k-blocks) take 2-tile
 // sub-records, so two 46-KiB slots and the spline slabs fit one CU's LDS
-#ifndef NFK_AR_NS_WIDE
-#define NFK_AR_NS_WIDE 2  // (diagnostic A/B: 1-tile sub-records for the wide conditioners)
-#endif
-#ifdef NFK_AR_DIAG_NS2  // diagnostic: 2-tile sub-records for every width
-__host__ __device__ constexpr int ar_ns_for(int) { return 2; }
-#else
-__host__ __device__ constexpr int ar_ns_for(int kbh) { return kbh <= 4 ? kArNS : NFK_AR_NS_WIDE; }
-#endif
+constexpr int kArNSWide = 2;
+__host__ __device__ constexpr int ar_ns_for(int kbh) { return kbh <= 4 ? kArNS : kArNSWide; }
 // waves per SIMD the register allocation targets: two for the NSF_CL-sized
 // conditioners, one (512 registers: MFMA accumulators in AGPRs) for the wide
 // ones, which run 4-wave workgroups only (NFK_AR_WAVES is not applied)
-#ifdef NFK_AR_DIAG_ONEWAVE  // diagnostic: every width compiled for one wave per SIMD (512 registers)
-__host__ __device__ constexpr int ar_min_waves(int) { return 1; }
-#else
 __host__ __device__ constexpr int ar_min_waves(int kbh) { return kbh <= 4 ? 2 : 1; }
-#endif
 // waves per workgroup, 16 samples each: 4 (one per SIMD; two independent
 // workgroups share a CU, so the two waves on a SIMD run unsynchronised phases)
 // or 8 (one workgroup per CU; half the weight stream per sample, but its two
@@ -132,11 +119,7 @@ inline size_t ar_lds_bytes(const ArDims& d, int dim, bool inv, int nw = kArWaves
     X(3, 1, 32, 4)  /* config.py defaults: H = 100, K 32 (nsplines), dim <= 64 */                \
     X(11, 1, 32, 6) /* Einstein / LJ.yaml: H = 354 (11 k-blocks + 2), K 32, 32 x 3 = 96 coords */ \
     X(11, 1, 32, 11) /* Fe_*.yaml: H = 354, K 32, 54 particles x 3 = 162 coordinates (<= 177) */ \
-    X(3, 1, 32, 6)  /* config.py defaults (H = 100, K 32) at 32 particles x 3 dims: dim <= 97 */ \
-    NFK_AR_DIAG_SHAPES(X)
-#ifndef NFK_AR_DIAG_SHAPES
-#define NFK_AR_DIAG_SHAPES(X)
-#endif
+    X(3, 1, 32, 6)  /* config.py defaults (H = 100, K 32) at 32 particles x 3 dims: dim <= 97 */
 
 inline bool ar_instance(const ArDims& d, int K, int* kbx) {
 #define NFK_AR_CHK(h, t, k, x)                                          \
@@ -304,21 +287,6 @@ __device__ __forceinline__ void trig_split(float v, float pi, float bnd, _Float1
     sl = (_Float16)(s - (float)sh);
 }
 
-#ifdef NFK_AR_DIAG_DUMP  // diagnostic: conditioner 1's activations and logits of workgroup 0
-__device__ float g_ar_dbg[3 * 64 * 512];
-template <int HT>
-__device__ void ar_dump_act(int stage, const f32x4 (&h)[HT], int kbh, int row, int q) {
-    for (int t = 0; t < HT; ++t)
-        for (int r = 0; r < 4; ++r) {
-            const int f = hid_feature(t, 4 * q + r, kbh);
-            if (f < 512) g_ar_dbg[(stage * 64 + row) * 512 + f] = h[t][r] * (1.0f / kActScale);
-        }
-}
-extern "C" int nfk_ar_dbg_copy(float* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ar_dbg), sizeof(g_ar_dbg), 0, hipMemcpyDeviceToHost);
-}
-#endif
-
 template <int KBH, int TK, int K, int KBX, bool INV, int NW>
 __device__ __forceinline__ void ar_layer(ArArgs a) {
     constexpr int kArWaves = NW;
@@ -414,15 +382,8 @@ __device__ __forceinline__ void ar_layer(ArArgs a) {
     auto slot = [&]() -> const float4* { return (s & 1) ? slot1 : slot0; };
     auto end = [&]() {
         gemm_fence();
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_barrier();
         stage_next();  // sub-record s + 2
-#ifdef NFK_AR_DIAG_SYNC  // diagnostic: every copy waited for at once (no copy in flight during a GEMM)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-#endif
         ++s;
     };
     const float c21 = -2.0f * kL2E * un1, c22 = -2.0f * kL2E * un2;
@@ -491,25 +452,14 @@ __device__ __forceinline__ void ar_layer(ArArgs a) {
                 ar_parts16<NS, KBH, NO, 0>(bh, bl, b1, b2, lane, o, slot, end, busy);
             } else {
                 act_operands<KBH, T1, HT>(h, c21, bh, bl, btail);
-#ifdef NFK_AR_DIAG_DUMP
-                if (i == 1 && blockIdx.x == 0) ar_dump_act<HT>(0, h, KBH, wid * 16 + sl, q);
-#endif
                 {
                     f32x4 h2[HT];
                     ar_parts<NS, KBH, T1, HT, 0>(bh, bl, btail, lane, h2, slot, end, 1.0f, busy);
                     act_operands<KBH, T1, HT>(h2, c22, bh, bl, btail);
-#ifdef NFK_AR_DIAG_DUMP
-                    if (i == 1 && blockIdx.x == 0) ar_dump_act<HT>(1, h2, KBH, wid * 16 + sl, q);
-#endif
                 }
                 ar_parts<NS, KBH, T1, NO, 0>(bh, bl, btail, lane, o, slot, end, 1.0f, busy);
             }
             // logits (unscaled: the exact power of two) into the slab, [sample][param]
-#ifdef NFK_AR_DIAG_DUMP
-            if (i == 1 && blockIdx.x == 0)
-                for (int t = 0; t < NO; ++t)
-                    for (int r = 0; r < 4; ++r) g_ar_dbg[(2 * 64 + wid * 16 + sl) * 512 + 16 * t + 4 * q + r] = o[t][r] * un3;
-#endif
 #pragma unroll
             for (int t = 0; t < NO; ++t) {
                 const int p = 16 * t + 4 * q;
@@ -708,10 +658,7 @@ template <int KBH, int T1, int K, int KBX>
 int launch_ar(const ArArgs& a, const ArDims& d, bool inv, hipStream_t st) {
     constexpr bool wide = ar_min_waves(KBH) == 1;  // one workgroup of 4 waves per CU
     const int nw = ar_waves(d);
-    size_t lds = ar_lds_bytes(d, a.dim, inv, nw);
-#ifdef NFK_AR_DIAG_PAD  // diagnostic: LDS padded to 96 KiB, one workgroup (one wave per SIMD) per CU
-    lds = lds < 96 * 1024 ? 96 * 1024 : lds;
-#endif
+    const size_t lds = ar_lds_bytes(d, a.dim, inv, nw);
     const int64_t nblk = a.csplit > 1 ? (a.rblocks * a.csplit + 7) / 8 * 8 : a.rblocks;
     const dim3 g((unsigned)nblk), b(64 * nw);
     if constexpr (wide) {
@@ -924,9 +871,7 @@ __device__ __forceinline__ void cl_layer(ClArgs a) {
     auto slot = [&]() -> const float4* { return (s & 1) ? slot1 : slot0; };
     auto end = [&]() {
         gemm_fence();
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_barrier();
         stage_next();
         ++s;
     };
@@ -1097,17 +1042,11 @@ int launch_cl(const ClArgs& a, const ArDims& d, bool inv, hipStream_t st) {
 // terms go to the workspace and k_ar_ld_sum adds them in column order
 // (bitwise any partition).  The inverse is sequential through the outputs
 // and stays on the per-column path.
-#ifndef NFK_ARS_KBS
-#define NFK_ARS_KBS 2
-#endif
-#ifndef NFK_ARS_NSL
-#define NFK_ARS_NSL 2
-#endif
-constexpr int kArsKBS = NFK_ARS_KBS;  // layer-1 k-blocks per sub-record
+constexpr int kArsKBS = 2;  // layer-1 k-blocks per sub-record
 // LDS slots of the sub-record ring: the copy of sub-record s + NSL is issued
 // at the barrier that ends s, and the wait before s + 1 counts only the copies
 // issued after s + 1's (vmcnt(n)), so NSL - 1 copies are in flight per GEMM
-constexpr int kArsNSL = NFK_ARS_NSL;
+constexpr int kArsNSL = 2;
 constexpr int kArsNW = 4;   // waves per workgroup (16 rows each)
 
 struct ArsDims {
@@ -1330,9 +1269,7 @@ __global__ __launch_bounds__(64 * kArsNW, 1) void k_fused_ar_s(ArsArgs a) {
     if (kArsNSL > 3) pq2 = stage_next();
     {
         wait_vmcnt_le(pq0 + pq1 + pq2);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();
     }
 
     int s = 0;  // sub-records consumed
@@ -1341,9 +1278,7 @@ __global__ __launch_bounds__(64 * kArsNW, 1) void k_fused_ar_s(ArsArgs a) {
         gemm_fence();
         // sub-record s + 1 landed: only the copies issued after it may be in flight
         wait_vmcnt_le(pq1 + pq2);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();
         const int c = stage_next();  // sub-record s + NSL, into the slot of s
         if (kArsNSL == 2) pq0 = c;
         if (kArsNSL == 3) pq0 = pq1, pq1 = c;

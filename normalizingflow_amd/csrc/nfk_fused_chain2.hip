@@ -262,24 +262,18 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                                               (NK == kRecA ? offA : (NK == kRecB ? offB : offC)) * 256;
         const float* g = Next::lane_src(rec, wid, lane);
         asm volatile("" : "+v"(g));  // formed here, not between the barriers
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();
         if (more) {
             Next::issue(g, wbase, wid);
         } else if (lyr + 1 < NL) {
             stage_record<kNsfWaves>(pkn + A->o_h1, A->blk_h1, slot, wid, lane);
         }
         if (!last) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            dma_barrier();
         }
     };
     auto epi_end = [&]() {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_barrier();
     };
     auto gemm_rec = [&](auto rk, auto& acc) {
         constexpr int N = sizeof(acc[0]) / sizeof(f32x4);
@@ -308,11 +302,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
             const float* src = A->x + (b0 + (r < nall ? r : (t0 < nall ? t0 : 0))) * A->ldx;
             for (int c0 = 0; c0 < D; c0 += 64)
                 if (c0 + lane < D) {
-#if NFK_X_NT
                     dma4_nt(src + c0 + lane, base + (r * XS + c0) * 4);
-#else
-                    dma4(src + c0 + lane, base + (r * XS + c0) * 4);
-#endif
                 }
         }
     }
@@ -448,7 +438,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                         const float v = xt[(16 * s + sl) * XS + tc4[r]];
                         xv[s][r] = (full_up || jj4[r] < A->n_up) ? v : 0.0f;
                     }
-                    knot_phase<K, true, 0, 4, true>(acc[s], xv[s], c, l2e3, kb[s], INV ? ch_k[s] : cw_k[s],
+                    knot_phase<K, true, 0, 4>(acc[s], xv[s], c, l2e3, kb[s], INV ? ch_k[s] : cw_k[s],
                                                    INV ? h_k[s] : w_k[s], scr + s * K * 64, lane);
                 }
             }
@@ -458,7 +448,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                 gemm_rec(RecB{}, acc);
 #pragma unroll
                 for (int s = 0; s < NTL; ++s)
-                    knot_phase<K, false, 0, 4, true>(acc[s], xv[s], c, l2e3, kb[s], INV ? cw_k[s] : ch_k[s],
+                    knot_phase<K, false, 0, 4>(acc[s], xv[s], c, l2e3, kb[s], INV ? cw_k[s] : ch_k[s],
                                                     INV ? w_k[s] : h_k[s], scr + s * K * 64, lane);
             }
             epi_end();

@@ -14,32 +14,13 @@ int nfk_set_error(const char* msg);  // nfk_kernels.hip
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef NFK_WAVES
-#define NFK_WAVES 8
-#endif
-#ifndef NFK_NSF_WAVES
-#define NFK_NSF_WAVES 4  // waves per workgroup of k_fused_nsf (one per SIMD)
-#endif
-#ifndef NFK_SPLIT_NS
-#define NFK_SPLIT_NS 4  // split form: tiles per sub-record (KBH <= 3)
-#endif
-#ifndef NFK_NSF_WPE_SPLIT
-#define NFK_NSF_WPE_SPLIT 3  // split form: workgroups per CU (waves per SIMD)
-#endif
-#ifndef NFK_GEMM_PF
-#define NFK_GEMM_PF 1  // gemm_h: prefetch the next tile pair's A fragments (register ring)
-#endif
-#ifndef NFK_SPLIT_PIPE
-#define NFK_SPLIT_PIPE 1  // split form: pipelined chunk schedule where it applies
-#endif
-#ifndef NFK_LDS_PAD
-#define NFK_LDS_PAD 0  // diagnostic: extra LDS per k_fused_nsf workgroup (fewer per CU)
-#endif
-
 namespace nfk_fused {
 
-constexpr int kWaves = NFK_WAVES;  // waves per workgroup (two per SIMD by default), 16 samples each
-constexpr int kNsfWaves = NFK_NSF_WAVES;
+constexpr int kWaves = 8;       // waves per workgroup (two per SIMD), 16 samples each
+constexpr int kNsfWaves = 4;    // waves per workgroup of k_fused_nsf (one per SIMD)
+constexpr int kSplitNs = 4;     // split form: tiles per sub-record (KBH <= 3)
+constexpr int kNsfWpeSplit = 3; // split form: workgroups per CU (waves per SIMD)
+constexpr int kNsfWpe = 2;      // whole-record form: waves per SIMD the register budget is sized for
 constexpr int kMaxD = 128;
 constexpr int kLdsBytes = 160 * 1024;
 constexpr float kActScale = 16384.0f;  // tanh outputs are split at 2^14 (|h| * 2^14 <= 2^14)
@@ -145,14 +126,13 @@ inline size_t lds_bytes(const Layout& L) {
     const int D = L.n_lo + L.n_up;
     const size_t maps = (size_t)((2 * D + 3) / 4) * 16;
     return (size_t)L.slot_blocks * 1024 + maps + (size_t)kNsfWaves * x_tile_floats(L) * sizeof(float) +
-           (size_t)kNsfWaves * L.K * 64 * sizeof(int) +  // bin lookup tables
-           NFK_LDS_PAD;
+           (size_t)kNsfWaves * L.K * 64 * sizeof(int);  // bin lookup tables
 }
 
 // Split form (NfkSplit): slot of KBH NS 2 + T1 NS/2 + 1 blocks (at least the
 // layer-1 record); used when three workgroups then fit a CU.
 inline int split_slot_blocks(const Layout& L) {
-    const int ns = L.KBH <= 3 ? NFK_SPLIT_NS : 2;
+    const int ns = L.KBH <= 3 ? kSplitNs : 2;
     const int sb = L.KBH * ns * 2 + (L.T1 ? (ns + 1) / 2 : 0) + 1;
     return sb > L.blk_h1 ? sb : L.blk_h1;
 }
@@ -161,8 +141,7 @@ inline int split_slot_blocks(const Layout& L) {
 inline size_t lds_bytes_split(const Layout& L) {
     const int D = L.n_lo + L.n_up;
     return (size_t)split_slot_blocks(L) * 1024 + (size_t)((3 * D + 3) / 4) * 16 +
-           (size_t)kNsfWaves * 16 * (D + 1) * sizeof(float) + (size_t)kNsfWaves * L.K * 64 * sizeof(int) +
-           NFK_LDS_PAD;
+           (size_t)kNsfWaves * 16 * (D + 1) * sizeof(float) + (size_t)kNsfWaves * L.K * 64 * sizeof(int);
 }
 // chain form: the maps region holds (nl + 1) D ints instead of 3 D
 inline size_t lds_bytes_chain(const Layout& L, int nl) {
@@ -172,7 +151,7 @@ inline size_t lds_bytes_chain(const Layout& L, int nl) {
 // shape conditions of the split form (the launch also needs 16-B aligned x
 // and z rows: D, ldx, ldz multiples of 4)
 inline bool split_ok(const Layout& L) {
-    return L.wide == 0 && (L.n_lo + L.n_up) % 4 == 0 && NFK_NSF_WPE_SPLIT * lds_bytes_split(L) <= (size_t)kLdsBytes;
+    return L.wide == 0 && (L.n_lo + L.n_up) % 4 == 0 && kNsfWpeSplit * lds_bytes_split(L) <= (size_t)kLdsBytes;
 }
 
 // most layers one chain launch may hold with three workgroups per CU (status
@@ -185,7 +164,7 @@ inline size_t lds_alloc(size_t b) { return (b + kLdsGranule - 1) / kLdsGranule *
 inline int chain_max_layers(const Layout& L) {
     if (!split_ok(L) || L.n_lo + L.n_up > 128) return 0;
     int n = 0;
-    while (n < 64 && NFK_NSF_WPE_SPLIT * lds_alloc(lds_bytes_chain(L, n + 1)) <= (size_t)kLdsBytes) ++n;
+    while (n < 64 && kNsfWpeSplit * lds_alloc(lds_bytes_chain(L, n + 1)) <= (size_t)kLdsBytes) ++n;
     return n;
 }
 
@@ -286,12 +265,9 @@ __device__ __forceinline__ void dma4(const float* gsrc, uint32_t lds) {
 
 // dma4 with the non-temporal cache policy: for bytes one workgroup reads once
 // (x rows), so they do not displace the weight records every workgroup re-reads.
-// NFK_X_NT: the chains' x rows (c3, c2) by this policy -- HBM traffic per launch
+// The chains' x rows (c3, c2) go by this policy: HBM traffic per launch
 // 1.27x -> 1.09x of the algorithmic bytes at c3, 1.14x -> 1.09x at c2, time
 // within 0.3 % (profiles/r5/r5zc_c3_x_nt_ab.txt, r5zd_c2_x_nt_ab.txt)
-#ifndef NFK_X_NT
-#define NFK_X_NT 1
-#endif
 __device__ __forceinline__ void dma4_nt(const float* gsrc, uint32_t lds) {
     uint32_t saved;  // m0 is reserved by the compiler: restore it
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
@@ -337,6 +313,12 @@ __device__ __forceinline__ void wait_vmcnt_le(int n) {
 
 __device__ __forceinline__ void dma_barrier() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// every LDS access of this wave retired (copies may stay in flight), then the barrier
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
@@ -390,35 +372,13 @@ __device__ __forceinline__ void gather_x(const float* __restrict__ x, int64_t ld
 // sign(x) (1 - t) / (1 + t), t = 2^(-2|x| log2e) in (0, 1]; c2 = -2 log2e
 // unscale.  Branch free, no overflow; absolute error ~1e-7 of the activation
 // (which only feeds the next linear layer, where absolute error propagates).
-// NFK_TANH6: 1 (default) 2^14 tanh = 2^15 / (1 + t) - 2^14 on t = e^(-2|x|), 6 VALU;
-// 0 the rounds 1-4 form (1 - t) / ((1 + t) / 2^14), 7 VALU; 2 a 5-VALU signed form.
-// A/B on one box (profiles/r5/r5s_tanh_ab.txt, kernel means of 3 runs): c2 chain
-// 4.849 / 4.702 / 4.768 ms, c3 chain 5.407 / 5.370 / 5.405 ms, Gaussian NSF_AR
-// 6.16 / - / 6.01 ms for 0 / 1 / 2; parity vs the oracle unchanged (7.6e-7 max rel.)
-#ifndef NFK_TANH6
-#define NFK_TANH6 1
-#endif
-#ifndef NFK_SPLIT_MIX
-#define NFK_SPLIT_MIX 1
-#endif
+// Computed as 2^15 / (1 + t) - 2^14 (6 VALU).  Tried: the 7-VALU form
+// (1 - t) / ((1 + t) / 2^14) and a 5-VALU signed form without |x|; this one was
+// fastest on the c2 and c3 chains (profiles/r5/r5s_tanh_ab.txt).
 __device__ __forceinline__ float tanh_scaled(float acc, float c2) {
-#if NFK_TANH6 == 2
-    // (A/B) 2^14 tanh(x) = 2^14 - 2^15 / (1 + e^(2x)) on the signed x: e^(2x)
-    // overflows to +inf for large x (the quotient to 0, tanh to 1) and
-    // underflows to 0 for large -x (tanh -1), so neither |x| nor copysign is
-    // needed: 5 VALU (mul, exp, add, rcp, fma)
-    const float t = __builtin_amdgcn_exp2f(acc * -c2);
-    return __builtin_fmaf(-2.0f * kActScale, __builtin_amdgcn_rcpf(1.0f + t), kActScale);
-#else
     const float t = __builtin_amdgcn_exp2f(__builtin_fabsf(acc) * c2);
-#if NFK_TANH6  // (A/B) 2^14 tanh = 2^15 / (1 + t) - 2^14: one VALU fewer
     const float r = __builtin_fmaf(2.0f * kActScale, __builtin_amdgcn_rcpf(1.0f + t), -kActScale);
-#else
-    const float inv = 1.0f / kActScale;
-    const float r = (1.0f - t) * __builtin_amdgcn_rcpf(__builtin_fmaf(t, inv, inv));
-#endif
     return __builtin_copysignf(r, acc);
-#endif
 }
 
 // the fp16 residuals of (v0, v1) over their fp16 roundings (the halves of
@@ -427,19 +387,12 @@ __device__ __forceinline__ float tanh_scaled(float acc, float c2) {
 // with an fp16 result, written into either half of the packed pair, that is
 // ONE v_fma_mix{lo,hi}_f16 per element instead of an fp16 -> fp32 convert, a
 // subtract and an fp32 -> fp16 convert (hipcc turns fma(h, -1, v) back into the
-// subtract, hence the asm).  NFK_SPLIT_MIX=0: the plain expression.
+// subtract, hence the asm).
 __device__ __forceinline__ uint32_t f16_residual_pair(float v0, float v1, uint32_t hp) {
-#if NFK_SPLIT_MIX
     uint32_t r;
     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hp), "v"(v0));
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(hp), "v"(v1));
     return r;
-#else
-    const _Float16 h0 = __builtin_bit_cast(_Float16, (uint16_t)(hp & 0xFFFFu));
-    const _Float16 h1 = __builtin_bit_cast(_Float16, (uint16_t)(hp >> 16));
-    const _Float16 l0 = (_Float16)(v0 - (float)h0), l1 = (_Float16)(v1 - (float)h1);
-    return (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
-#endif
 }
 
 // B fragments (hi, lo) of k-block kb from the activations of tiles 2kb, 2kb+1
@@ -447,24 +400,19 @@ template <int HT>
 __device__ __forceinline__ void split_act(const f32x4 (&a)[HT], int kb, h8& hi, h8& lo) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) hi[j] = (_Float16)a[2 * kb + (j >> 2)][j & 3];
-#if NFK_SPLIT_MIX
     const u32x4 hp = __builtin_bit_cast(u32x4, hi);
     u32x4 lp;
 #pragma unroll
     for (int p = 0; p < 4; ++p)
         lp[p] = f16_residual_pair(a[2 * kb + (p >> 1)][2 * (p & 1)], a[2 * kb + (p >> 1)][2 * (p & 1) + 1], hp[p]);
     lo = __builtin_bit_cast(h8, lp);
-#else
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lo[j] = (_Float16)(a[2 * kb + (j >> 2)][j & 3] - (float)hi[j]);
-#endif
 }
 
 // Wait after a GEMM's last MFMA before its accumulators are read (32 wait
 // states).  Measured on the wide fused NSF_AR (nfk_fused_ar.hip, one wave per
 // SIMD, accumulators in AGPRs): without it the last output tile's register 3
 // (the MFMA's last-written rows) was read stale in some builds -- the compiler's
-// own MFMA -> read wait states did not cover it (tools/dbg_ar_dump.py,
+// own MFMA -> read wait states did not cover it (an activation dump of that round,
 // profiles/r4_ar_wide_debug.txt).
 // Fence that ends a GEMM segment before its workgroup barrier.  The barrier
 // and the copy waits are inline asm, which orders memory operations only: the
@@ -494,7 +442,9 @@ __device__ __forceinline__ void mfma_result_wait() {
 // Tiles go in pairs whose MFMAs alternate accumulators: a dependent MFMA
 // chain blocks the SIMD partner wave's VALU, two interleaved chains let it
 // overlap (tools/ubench_coexec2.hip, modes 5-6).  A fragments of the next
-// pair are read from the LDS slot while the current pair's MFMAs run.
+// pair are read from the LDS slot while the current pair's MFMAs run (without
+// this prefetch ring the c3 chain took 6.24/6.35 vs 6.15/6.19 ms: DESIGN.md
+// section 6).
 // Split form (sub-records, k_fused_nsf<..., SPLIT = true>): the slot holds
 // tiles [T0, T0 + NT) of a record, at a tile stride of NS per k-block, then
 // the tail blocks holding them and the record's whole bias block; acc has NA
@@ -503,7 +453,7 @@ __device__ __forceinline__ void mfma_result_wait() {
 // of more than 16 tiles, whose biases exceed one 1-KiB block); else the
 // record's whole bias block (tile t at row t).
 // WAIT: the last MFMA's results are read soon after (a record's last
-// sub-record): wait them out here (see kMfmaResultWait).
+// sub-record): wait them out here (see mfma_result_wait).
 template <int KBH, bool T1, int NT, int NS = NT, int T0 = 0, int NA = NT, bool BREL = false, bool WAIT = false>
 __device__ __forceinline__ void gemm_h(const h8 (&bh)[KBH], const h8 (&bl)[KBH], h4 btail,
                                        const float4* slot, int lane, f32x4 (&acc)[NA], float bsc = 1.0f) {
@@ -516,11 +466,6 @@ __device__ __forceinline__ void gemm_h(const h8 (&bh)[KBH], const h8 (&bl)[KBH],
     const float4* bias = tail + NTG * 64;
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[T0 + t] = as_f32x4(bias[((BREL ? 0 : T0) + t) * 4 + q]) * bsc;
-#ifdef NFK_DIAG_BIAS_NOP  // diagnostic: a wait between the bias initialisation and the first MFMA
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     // fragments of step i into a ring slot: k-block step i = (kb, pr): tile
     // t0 = 2 pr {hi, lo}, tile t0 + 1 {hi, lo}; tail step N + pr: one 16-B
     // word per lane holding both tiles' tail fragments (tail block pr)
@@ -535,15 +480,12 @@ __device__ __forceinline__ void gemm_h(const h8 (&bh)[KBH], const h8 (&bl)[KBH],
         }
     };
     float4 ring[2][4];
-    if constexpr (NFK_GEMM_PF) fetch(0, ring[0]);
+    fetch(0, ring[0]);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int pr = i < N ? i % NPR : i - N, kb = i < N ? i / NPR : 0, t0 = T0 + 2 * pr;
         const bool two = t0 + 1 < T0 + NT;
-        if constexpr (!NFK_GEMM_PF)  // no prefetch: the step's fragments just before its MFMAs
-            fetch(i, ring[i & 1]);
-        else if (i + 1 < NI)
-            fetch(i + 1, ring[(i + 1) & 1]);
+        if (i + 1 < NI) fetch(i + 1, ring[(i + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
         const float4* r = ring[i & 1];
         if (i >= N) {  // tail step (T1)
@@ -556,9 +498,6 @@ __device__ __forceinline__ void gemm_h(const h8 (&bh)[KBH], const h8 (&bl)[KBH],
                 __builtin_amdgcn_sched_barrier(0);
                 if (NT == 1) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7");
                 else asm volatile("s_nop 7\n\ts_nop 7");
-#ifdef NFK_TAIL_NOP_EXTRA  // diagnostic: a longer wait before the tail step
-                asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7");
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             const float4 w = r[0];
@@ -567,23 +506,14 @@ __device__ __forceinline__ void gemm_h(const h8 (&bh)[KBH], const h8 (&bl)[KBH],
             continue;
         }
         const h8 ahi0 = __builtin_bit_cast(h8, r[0]), alo0 = __builtin_bit_cast(h8, r[1]);
-#ifdef NFK_DIAG_MFMA_NOP  // diagnostic: a wait between the alternating MFMAs of a tile pair
-#define NFK_MN() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 7\n\ts_nop 3"); \
-                      __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define NFK_MN() do { } while (0)
-#endif
         if (two) {
             const h8 ahi1 = __builtin_bit_cast(h8, r[2]), alo1 = __builtin_bit_cast(h8, r[3]);
             acc[t0] = mfma16(alo0, bh[kb], acc[t0]);
             acc[t0 + 1] = mfma16(alo1, bh[kb], acc[t0 + 1]);
-            NFK_MN();
             acc[t0] = mfma16(ahi0, bl[kb], acc[t0]);
             acc[t0 + 1] = mfma16(ahi1, bl[kb], acc[t0 + 1]);
-            NFK_MN();
             acc[t0] = mfma16(ahi0, bh[kb], acc[t0]);
             acc[t0 + 1] = mfma16(ahi1, bh[kb], acc[t0 + 1]);
-            NFK_MN();
         } else {
             acc[t0] = mfma16(alo0, bh[kb], acc[t0]);
             acc[t0] = mfma16(ahi0, bl[kb], acc[t0]);
@@ -655,23 +585,14 @@ __device__ __forceinline__ void act_operands(f32x4 (&h)[HT], float c2, h8 (&bh)[
 // the bin of utils.py:20-25 for every x inside the tails (edges are strictly
 // increasing; elements within an ulp of an edge may take the neighbouring
 // bin, where the C1 spline agrees); the other phase selects by k.
-// NFK_LUT (default): the two prefixes at the bin are read back from a per-wave
-// LDS table (row j = prefix j of every lane, one ds_read2st64 at row k)
-// instead of 2 (K-1) selects on compare masks.
-#ifndef NFK_LUT
-#define NFK_LUT 1
-#endif
-#ifndef NFK_E1_SEL
-// knot_phase: the bin's right edge computed for every lane, then selected
-#define NFK_E1_SEL 1
-#endif
-#ifndef NFK_PK2
-// knot prefixes of coordinate pairs in packed fp32: 7 % fewer VALU
-// instructions per layer, yet c3 measured 1 % slower (6.37 vs 6.30 ms per
-// chain, A/B on one box), so off by default
-#define NFK_PK2 0
-#endif
-template <int K, bool SEARCH, int R0 = 0, int R1 = 4, bool PK = true>
+// The two prefixes at the bin are read back from a per-wave LDS table (row j =
+// prefix j of every lane, one ds_read2st64 at row k).  Tried: 2 (K-1) selects on
+// compare masks, c3 6.69 vs 6.28 ms per chain, and an
+// unsigned-minimum search without the table (section 10).
+// Tried: the knot prefixes of coordinate pairs in packed fp32 -- 7 % fewer VALU
+// instructions per layer, yet c3 measured 1 % slower (6.37 vs 6.30 ms per chain,
+// A/B on one box, profiles/r2_c3_flags_ab.txt).
+template <int K, bool SEARCH, int R0 = 0, int R1 = 4>
 __device__ __forceinline__ void knot_phase(const f32x4 (&acc)[K], const float (&xv)[4],
                                            const FusedConst& c, float l2e, int (&kb)[4],
                                            float (&ek)[4], float (&sk)[4], int* scr, int lane) {
@@ -687,38 +608,17 @@ __device__ __forceinline__ void knot_phase(const f32x4 (&acc)[K], const float (&
     }
     return;
 #endif
-    // coordinate pairs (r, r + 1): the knot prefixes of both in packed fp32
-    // (nfk_prefix_nsf_lean2, NFK_PK2; bitwise the per-coordinate result)
-    constexpr bool PAIRS = PK && NFK_PK2 && K <= 8 && (R1 - R0) % 2 == 0;
-    int pre2[K];
-    float s2b = 0.0f;
 #pragma unroll
     for (int r = R0; r < R1; ++r) {
         float u[K];
         int pre[K];
-        float s2;  // the second softmax's sum: NaN iff a logit was NaN
 #pragma unroll
         for (int t = 0; t < K; ++t) u[t] = acc[t][r];
-        if constexpr (PAIRS) {
-            if ((r - R0) % 2 == 0) {
-                float u1[K];
-#pragma unroll
-                for (int t = 0; t < K; ++t) u1[t] = acc[t][r + 1];
-                const nfk_f2 s = nfk_prefix_nsf_lean2<K>(u, u1, l2e, c.m2b, c.fb30, c.mb30, pre, pre2);
-                s2 = s.x;
-                s2b = s.y;
-            } else {
-#pragma unroll
-                for (int t = 0; t < K; ++t) pre[t] = pre2[t];
-                s2 = s2b;
-            }
-        } else {
-            s2 = nfk_prefix_nsf_lean<K>(u, l2e, c.m2b, c.fb30, c.mb30, pre);
-        }
+        // the second softmax's sum: NaN iff a logit was NaN
+        const float s2 = nfk_prefix_nsf_lean<K>(u, l2e, c.m2b, c.fb30, c.mb30, pre);
         // the knot range's left end, NaN iff the logits were: the reference's NaN
         // cumsum makes every edge NaN (the integer prefixes would drop it)
         const float lo = __builtin_fmaf(s2, 0.0f, c.lo);
-        int p0 = 0, p1 = pre[1 < K ? 1 : 0];
         if (SEARCH) {
             const int xi = __float2int_rd(__builtin_fmaf(xv[r], c.inv30, -c.lo * c.inv30));
             int k = 0;
@@ -727,41 +627,16 @@ __device__ __forceinline__ void knot_phase(const f32x4 (&acc)[K], const float (&
             kb[r] = k;
         }
         const int kk = kb[r];
-        if (NFK_LUT == 2 && SEARCH) {
-            // (diagnostic A/B) the searched phase without the table: the
-            // prefixes are strictly increasing from pre[0] = 0, so pre[kk] is
-            // the largest prefix <= xi and pre[kk + 1] the smallest > xi, each
-            // an unsigned minimum of differences (negative ones wrap high)
-            const int xi = __float2int_rd(__builtin_fmaf(xv[r], c.inv30, -c.lo * c.inv30));
-            uint32_t m0 = (uint32_t)xi, m1 = 0xffffffffu;
+        // rows 0..K-1; p1 is unused when kk = K - 1 (e1 = hi below)
 #pragma unroll
-            for (int j = 1; j < K; ++j) {
-                m0 = min(m0, (uint32_t)xi - (uint32_t)pre[j]);
-                m1 = min(m1, (uint32_t)pre[j] - (uint32_t)xi - 1u);
-            }
-            p0 = (int)((uint32_t)xi - m0);
-            p1 = (int)((uint32_t)xi + 1u + m1);
-        } else if (NFK_LUT) {
-            // rows 0..K-1; p1 is unused when kk = K - 1 (e1 = hi below)
-#pragma unroll
-            for (int j = 0; j < K; ++j) scr[j * 64 + lane] = pre[j];
-            p0 = scr[kk * 64 + lane];
-            p1 = scr[(kk + 1 < K ? kk + 1 : K - 1) * 64 + lane];
-        } else {
-#pragma unroll
-            for (int j = 1; j < K; ++j) {
-                const bool ge = kk >= j;
-                p0 = ge ? pre[j] : p0;
-                if (j + 1 < K) p1 = ge ? pre[j + 1] : p1;
-            }
-        }
+        for (int j = 0; j < K; ++j) scr[j * 64 + lane] = pre[j];
+        const int p0 = scr[kk * 64 + lane];
+        const int p1 = scr[(kk + 1 < K ? kk + 1 : K - 1) * 64 + lane];
         const float e = __builtin_fmaf(c.sp30, (float)p0, lo);
         float e1 = __builtin_fmaf(c.sp30, (float)p1, lo);
         // computed for every lane, then selected: as a conditional the compiler
         // sank the LUT read into a branch with its own LDS wait
-#if NFK_E1_SEL
         asm volatile("" : "+v"(e1));
-#endif
         e1 = (kk == K - 1) ? c.hi : e1;
         ek[r] = e;
         sk[r] = e1 - e;
@@ -815,7 +690,7 @@ __device__ __forceinline__ void stage_phase(const FusedArgs& a, const float* __r
 // slot shrinks to KBH NS 2 + 2 blocks and three workgroups share a CU.
 template <int KBH, bool T1, int K, int HT>
 struct NfkSplit {
-    static constexpr int NS = KBH <= 3 ? NFK_SPLIT_NS : 2;  // tiles per sub-record
+    static constexpr int NS = KBH <= 3 ? kSplitNs : 2;  // tiles per sub-record
     static constexpr int NH2 = (HT + NS - 1) / NS;   // layer-2 sub-records
     static constexpr int NW = (K + NS - 1) / NS;     // W (or H) logits sub-records
     static constexpr int ND = (K - 1 + NS - 1) / NS; // derivative logits sub-records
@@ -904,17 +779,13 @@ __device__ __forceinline__ void gemm_parts(const h8 (&bh)[KBH], const h8 (&bl)[K
     if constexpr (!last) gemm_parts<KBH, T1, NT, NS, J + 1>(bh, bl, btail, slot, lane, acc, step);
 }
 
-#ifndef NFK_NSF_WPE
-#define NFK_NSF_WPE 2  // waves per SIMD the register budget is sized for
-#endif
-
 // CHAIN (split form only): a.nlayers layers in one launch.  The wave's x rows
 // stay in its LDS tile from the first layer to the last (layer l reads and
 // overwrites the tile columns a.cmaps gives it), log|det| is carried in a
 // register and the status bits in LDS words, and the layer-1 record of layer l + 1 is copied
 // during the last epilogue of layer l: one prologue and one tail per chain.
 template <int KBH, bool T1, int K, bool INV, bool SPLIT, bool CHAIN = false>
-__global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF_WPE) void k_fused_nsf(FusedArgs a) {
+__global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? kNsfWpeSplit : kNsfWpe) void k_fused_nsf(FusedArgs a) {
     static_assert(SPLIT || !CHAIN, "the chain form is a split-form kernel");
     // the arguments through a pointer the chain form re-derives opaquely at
     // every layer, so values loaded from them are not hoisted out of the layer
@@ -926,9 +797,8 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF
     constexpr int DN = K - 1 > 0 ? K - 1 : 1;
     using SP = NfkSplit<KBH, T1, K, HT>;
     // pipelined chunk schedule: split form with two sub-records per W/H/D record
-    constexpr bool PIPE = SPLIT && NFK_SPLIT_PIPE && SP::NW == 2 && SP::ND == 2;
-    // packed knot prefixes, except in the inverse chain (it spills with them)
-    constexpr bool PK2 = !(INV && CHAIN);
+    // (the plain split schedule there: 6.21/6.17 vs 6.15/6.19 ms)
+    constexpr bool PIPE = SPLIT && SP::NW == 2 && SP::ND == 2;
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int q = lane >> 4, sl = lane & 15;
@@ -989,9 +859,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF
     int sr = 0;
     auto gemm_end = [&](bool last) {
         NFK_MARK(tr);  // GEMM issued
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        lds_barrier();
         NFK_MARK(tr);  // barrier passed
         if (sr + 1 < NSR) {
             if constexpr (SPLIT)
@@ -1005,16 +873,12 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF
         }
         ++sr;
         if (!last) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            dma_barrier();
         }
     };
     auto epi_end = [&]() {
         NFK_MARK(tr);  // epilogue issued
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_barrier();
         NFK_MARK(tr);  // barrier passed
     };
     // a GEMM over a whole record (acc: its NT tiles), then the step(s)
@@ -1226,12 +1090,12 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF
                 const float v = (SPLIT ? xlo : xup)[pos4[r]];
                 xv[r] = ok ? v : 0.0f;
             }
-            knot_phase<K, true, R0, R1, PK2>(acc, xv, c, l2e3, kb, INV ? ch_k : cw_k, INV ? h_k : w_k, scr, lane);
+            knot_phase<K, true, R0, R1>(acc, xv, c, l2e3, kb, INV ? ch_k : cw_k, INV ? h_k : w_k, scr, lane);
         };
         // epilogue B: the other knots, selected at the bin
         auto epi_b = [&](const f32x4(&acc)[K], auto r0c, auto r1c) {
             constexpr int R0 = decltype(r0c)::value, R1 = decltype(r1c)::value;
-            knot_phase<K, false, R0, R1, PK2>(acc, xv, c, l2e3, kb, INV ? cw_k : ch_k, INV ? w_k : h_k, scr, lane);
+            knot_phase<K, false, R0, R1>(acc, xv, c, l2e3, kb, INV ? cw_k : ch_k, INV ? w_k : h_k, scr, lane);
         };
         // epilogue C: derivatives of the bin, evaluate, log|det|
         auto epi_c = [&](const f32x4(&accd)[DN], auto r0c, auto r1c) {
@@ -1253,21 +1117,12 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? NFK_NSF_WPE_SPLIT : NFK_NSF
                 // padded derivative index j+1 holds logit j (utils.py:36-39):
                 // raw_k = logit k-1, raw_k1 = logit k
                 const int k = kb[r];
-                float raw_k = accd[0][r], raw_k1 = accd[0][r];
-                if (NFK_LUT) {
-                    // row j = logit j; raw_k is unused at k = 0, raw_k1 at k = K - 1
-                    float* fs = reinterpret_cast<float*>(scr);
+                // table row j = logit j; raw_k is unused at k = 0, raw_k1 at k = K - 1
+                float* fs = reinterpret_cast<float*>(scr);
     #pragma unroll
-                    for (int j = 0; j < K - 1; ++j) fs[j * 64 + lane] = accd[j][r];
-                    raw_k = fs[(k > 0 ? k - 1 : 0) * 64 + lane];
-                    raw_k1 = fs[(k < K - 1 ? k : K - 2) * 64 + lane];
-                } else {
-    #pragma unroll
-                    for (int j = 1; j < K - 1; ++j) {
-                        raw_k = (k >= j + 1) ? accd[j][r] : raw_k;
-                        raw_k1 = (k >= j) ? accd[j][r] : raw_k1;
-                    }
-                }
+                for (int j = 0; j < K - 1; ++j) fs[j * 64 + lane] = accd[j][r];
+                const float raw_k = fs[(k > 0 ? k - 1 : 0) * 64 + lane];
+                const float raw_k1 = fs[(k < K - 1 ? k : K - 2) * 64 + lane];
                 // d = min_d + softplus(softplus(D)) (flows.py:235, utils.py:82), only
                 // at the two knots the bin uses; the padded ends are the constant d_edge
                 // both evaluated, then selected: as a conditional the compiler

@@ -100,9 +100,7 @@ __device__ __forceinline__ void stage_rphase(const RArgs& a, int p, bool inv, fl
 
 __device__ __forceinline__ void rblock_end(int b, const RArgs& a, bool inv, float4* slot0, float4* slot1,
                                            int wid, int lane) {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    dma_barrier();
     if (b + 2 < 8) stage_rphase(a, b + 2, inv, slot0, slot1, wid, lane);
 }
 
@@ -478,9 +476,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_rnvp_chain(RChainArgs a) 
     // end of the GEMM of sub-record k (slot k & 1 = freed): this wave's reads
     // of it and its copy of k + 1 done, barrier, then the copy of k + 2 into it
     auto step = [&](float4* freed) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_barrier();
         stage_next(freed);
     };
 
@@ -496,22 +492,16 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_rnvp_chain(RChainArgs a) 
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (r < nrows && cc < n) {
                 const float4* src = reinterpret_cast<const float4*>(x + (b0 + r) * ldx + hf * n + cc);
-#if NFK_X_NT
                 // read once: the nt policy (see dma4_nt)
                 const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
                 v = make_float4(t[0], t[1], t[2], t[3]);
-#else
-                v = *src;
-#endif
             }
             *reinterpret_cast<float4*>(tile + r * RS + c) = v;
         }
     }
     stage_next(slot0);
     stage_next(slot1);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    dma_barrier();
 
     const bool row_ok = sl < nrows;
     float ld_acc = (q == 0 && row_ok && A->mode == 2) ? A->logdet[b0 + sl] : 0.0f;

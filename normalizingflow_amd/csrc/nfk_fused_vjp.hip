@@ -18,9 +18,6 @@
 // backward.  The records are re-cut into kVNS-tile sub-records of SB blocks
 // (the pack's VJP stream) and double-buffered through two LDS slots with one
 // barrier per sub-record (the RealNVP chain's schedule, nfk_fused_rnvp.hip).
-#ifndef NFK_VJP_FAST
-#define NFK_VJP_FAST 1  // hardware exp / rcp and an fp32 knot cumsum in the element backward
-#endif
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -86,24 +83,6 @@ __device__ __forceinline__ void store_act(const f32x4 (&h)[HT], float* row, int 
     if (q == 1) row[H] = 1.0f;
 }
 
-#ifdef NFK_VJP_DIAG_SAVE  // diagnostic: every element backward's inputs, [B][n_up][3K + 2] floats
-__device__ float* g_vjp_dbg;
-extern "C" int nfk_vjp_diag_set(float* p) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_vjp_dbg), &p, sizeof(p), 0, hipMemcpyHostToDevice);
-}
-#endif
-#ifdef NFK_VJP_DIAG_TWICE  // diagnostic: per-lane counts of elements whose two evaluations differed
-__device__ int g_vjp_cnt[64 + 80];  // per-lane mismatches, then per first-differing probe slot
-extern "C" int nfk_vjp_diag_counts(int* host, int reset) {
-    int rc = (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_vjp_cnt), sizeof(g_vjp_cnt), 0, hipMemcpyDeviceToHost);
-    if (reset) {
-        static const int zero[64 + 80] = {0};
-        rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_vjp_cnt), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-    }
-    return rc;
-}
-#endif
-
 template <int KBH, bool T1, int K, bool INV>
 __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
     constexpr VjpDims d = vjp_dims(KBH, T1 ? 1 : 0, K);
@@ -134,25 +113,15 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
     auto stage_next = [&](float4* slot) {
         if (nsub >= a.nsub) return;
         const float* src = a.stream + (int64_t)nsub * SB * 256;
-#ifdef NFK_VJP_DIAG_PLAIN  // diagnostic: plain loads + ds_write instead of LDS-DMA
-#pragma unroll
-        for (int i = 0; i < SB / 4; ++i)
-            slot[(wid + 4 * i) * 64 + lane] = *reinterpret_cast<const float4*>(src + (int64_t)(wid + 4 * i) * 256 + lane * 4);
-#else
         const uint32_t base = lds_addr(slot);
 #pragma unroll
         for (int i = 0; i < SB / 4; ++i)
             dma16(src + (int64_t)(wid + 4 * i) * 256 + lane * 4, base + (wid + 4 * i) * 1024);
-#endif
         ++nsub;
     };
     auto step = [&](float4* freed) {
-#ifndef NFK_VJP_NO_FENCE
         gemm_fence();
-#endif
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dma_barrier();
         stage_next(freed);
     };
 
@@ -172,9 +141,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
     }
     stage_next(slot0);
     stage_next(slot1);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    dma_barrier();
     int cur = 0;
     const float un1 = a.hdr[kHdrUnscale], un2 = a.hdr[kHdrUnscale + 1], un3 = a.hdr[kHdrUnscale + 2];
 
@@ -221,21 +188,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
         if (row_ok) store_act<KBH, T1, HT>(h2, a.h2 + b * a.ldh, q, a.H);
     }
     const float gl = (a.gld != nullptr) ? a.gld[b] : 0.0f;
-#ifdef NFK_VJP_DIAG_VGPRC  // diagnostic: the spline constants in VGPRs (no SGPR pressure from them)
-    NfkSplineConst cc = a.c;
-    asm volatile("" : "+v"(cc.scale2b), "+v"(cc.lo), "+v"(cc.hi), "+v"(cc.span), "+v"(cc.ylo), "+v"(cc.yhi),
-                 "+v"(cc.yspan), "+v"(cc.min_w), "+v"(cc.fw), "+v"(cc.min_h), "+v"(cc.fh));
-    asm volatile("" : "+v"(cc.min_d), "+v"(cc.dpad), "+v"(cc.knot_eps), "+v"(cc.m2b), "+v"(cc.d_edge));
-#else
     const NfkSplineConst& cc = a.c;
-#endif
-#ifdef NFK_VJP_DIAG_NOP
-#define NFK_VJP_NOPS() do { __builtin_amdgcn_sched_barrier(0); \
-        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7"); \
-        __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define NFK_VJP_NOPS() do { } while (0)
-#endif
     // ---- output layer in 8-coordinate chunks: W, H, D logits of the lane's two
     // coordinates in registers, then the spline VJP of each
     for (int ch = 0; ch < a.NCH; ++ch) {
@@ -243,7 +196,6 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
         vjp_parts<KBH, T1, KW, 0>(bh, bl, bt, slot0, slot1, cur, lane, aw, step);
         vjp_parts<KBH, T1, KW, 0>(bh, bl, bt, slot0, slot1, cur, lane, ah, step);
         vjp_parts<KBH, T1, KD, 0>(bh, bl, bt, slot0, slot1, cur, lane, ad, step);
-        NFK_VJP_NOPS();
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
             const int j = 8 * ch + 2 * q + cb;
@@ -258,75 +210,8 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
             }
             const float xv = tile[sl * XS + m_up_in[j]];
             const float go = (a.gz != nullptr) ? a.gz[b * a.ldgz + m_up_out[j]] : 0.0f;
-#ifdef NFK_VJP_DIAG_SAVE
-            if (row_ok) {
-                float* sv = g_vjp_dbg + (b * n_up + j) * (3 * K + 2);
-#pragma unroll
-                for (int i = 0; i < K; ++i) sv[i] = wr[i];
-#pragma unroll
-                for (int i = 0; i < K; ++i) sv[K + i] = hr[i];
-#pragma unroll
-                for (int i = 0; i < K - 1; ++i) sv[2 * K + i] = dr[i];
-                sv[3 * K - 1] = xv;
-                sv[3 * K] = go;
-                sv[3 * K + 1] = gl;
-            }
-#ifdef NFK_VJP_DIAG_RELOAD  // diagnostic: the element backward runs on the values just stored, re-read
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            {
-                volatile const float* rv = g_vjp_dbg + (b * n_up + j) * (3 * K + 2);
-#pragma unroll
-                for (int i = 0; i < K; ++i) wr[i] = rv[i];
-#pragma unroll
-                for (int i = 0; i < K; ++i) hr[i] = rv[K + i];
-#pragma unroll
-                for (int i = 0; i < K - 1; ++i) dr[i] = rv[2 * K + i];
-            }
-#endif
-#endif
-#ifdef NFK_VJP_DUMP  // diagnostic: the element backward's inputs instead of its outputs
-            const float gxv = xv + 1000.0f * go + 1.0e6f * gl;
-#else
-#ifdef NFK_VJP_DIAG_TWICE  // diagnostic: the element backward twice on the same registers; mismatches counted
-            float w2[K], h2[K], d2[K - 1];
-#pragma unroll
-            for (int i = 0; i < K; ++i) w2[i] = wr[i], h2[i] = hr[i];
-#pragma unroll
-            for (int i = 0; i < K - 1; ++i) d2[i] = dr[i];
-#ifdef NFK_BWD_PROBE
-            float pr1[nfk_bwd::kProbeSlots], pr2[nfk_bwd::kProbeSlots];
-#pragma unroll
-            for (int i = 0; i < nfk_bwd::kProbeSlots; ++i) pr1[i] = pr2[i] = 0.0f;
-#define NFK_PA1 , pr1
-#define NFK_PA2 , pr2
-#else
-#define NFK_PA1
-#define NFK_PA2
-#endif
-            const float gx2 = nfk_bwd::rqs_element_bwd<K, INV, true, false, NFK_VJP_FAST>(xv, w2, h2, d2, cc, go, gl NFK_PA2);
-            asm volatile("" ::: "memory");
-#endif
-#ifndef NFK_PA1
-#define NFK_PA1
-#endif
-            const float gxv = nfk_bwd::rqs_element_bwd<K, INV, true, false, NFK_VJP_FAST>(xv, wr, hr, dr, cc, go, gl NFK_PA1);
-#ifdef NFK_VJP_DIAG_TWICE
-            {
-                bool same = __float_as_uint(gx2) == __float_as_uint(gxv);
-#pragma unroll
-                for (int i = 0; i < K; ++i) same = same && __float_as_uint(w2[i]) == __float_as_uint(wr[i]);
-                if (!same && row_ok) atomicAdd(g_vjp_cnt + lane, 1);
-#ifdef NFK_BWD_PROBE
-                // the first intermediate (in computation order) where the two evaluations part
-                int first = -1;
-#pragma unroll
-                for (int i = nfk_bwd::kProbeSlots - 1; i >= 0; --i)
-                    first = __float_as_uint(pr1[i]) != __float_as_uint(pr2[i]) ? i : first;
-                if (first >= 0 && row_ok) atomicAdd(g_vjp_cnt + 64 + first, 1);
-#endif
-            }
-#endif
-#endif
+            // hardware exp / rcp and an fp32 knot cumsum in the element backward (FAST)
+            const float gxv = nfk_bwd::rqs_element_bwd<K, INV, true, false, true>(xv, wr, hr, dr, cc, go, gl);
             if (row_ok) {
                 a.gx[b * a.ldgx + m_up_in[j]] = gxv;
                 float* g = a.gp + (b * n_up + j) * P;
@@ -338,7 +223,6 @@ __global__ __launch_bounds__(64 * kNsfWaves, 3) void k_nsf_vjp(VjpArgs a) {
                 for (int i = 0; i < K - 1; ++i) g[2 * K + i] = dr[i];
             }
         }
-        NFK_VJP_NOPS();
     }
     // ---- lower coordinates: the identity part of dL/dx (flows.py:239)
     for (int i = lane; i < 16 * n_lo; i += 64) {
@@ -352,15 +236,7 @@ template <int KBH, int T1, int K>
 int launch_vjp(const VjpArgs& a, bool inv, hipStream_t st) {
     const int64_t blocks = (a.batch + kNsfWaves * 16 - 1) / (kNsfWaves * 16);
     if (blocks == 0) return 0;
-#ifdef NFK_VJP_DIAG_ONEWG  // diagnostic: LDS padded so that one workgroup runs per CU
-    const size_t lds = 96 * 1024;
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nsf_vjp<KBH, T1 != 0, K, false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nsf_vjp<KBH, T1 != 0, K, true>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#else
     const size_t lds = vjp_lds_bytes(vjp_dims(KBH, T1, K), a.n_lo + a.n_up);
-#endif
     if (inv)
         hipLaunchKernelGGL((k_nsf_vjp<KBH, T1 != 0, K, true>), dim3((unsigned)blocks), dim3(64 * kNsfWaves), lds,
                            st, a);

@@ -42,29 +42,14 @@
 
 namespace nfk_fused {
 
-// Frame size and workgroup shape.  Default: one 8-wave workgroup per CU,
-// 65-block frames.  NFK_WIDE_FB=32 NFK_WIDE_NW=4 builds two 4-wave workgroups
-// per CU with 33-block frames (measured 4-5 % slower at c5: twice the
-// sub-steps, and the two workgroups do not desynchronise usefully).
-#ifndef NFK_WIDE_FB
-#define NFK_WIDE_FB 64
-#endif
-#ifndef NFK_WIDE_NW
-#define NFK_WIDE_NW 8
-#endif
-#ifndef NFK_WIDE_PK
-#define NFK_WIDE_PK 1
-#endif
-#ifndef NFK_WIDE_PIN
-#define NFK_WIDE_PIN 1
-#endif
-constexpr int kWideFB = NFK_WIDE_FB;             // f16 blocks of a frame
+// Frame size and workgroup shape: one 8-wave workgroup per CU, 65-block
+// frames.  Tried: two 4-wave workgroups per CU with 33-block frames, 4-5 %
+// slower at c5 (twice the sub-steps, and the two workgroups do not
+// desynchronise usefully).
+constexpr int kWideFB = 64;                      // f16 blocks of a frame
 constexpr int kWideSlotBlocks = kWideFB + 1;     // + the record's bias block
-constexpr int kWideWaves = NFK_WIDE_NW;          // waves per workgroup
-constexpr int kWideWGs = kWideWaves == 4 ? 2 : 1;  // workgroups per CU
+constexpr int kWideWaves = 8;                    // waves per workgroup
 constexpr int kWideTile = 16 * 32;               // floats of a wave's chunk-pair tile
-static_assert(kWideFB == 32 || kWideFB == 64, "frame of 32 or 64 blocks");
-static_assert(kWideWaves == 4 || kWideWaves == 8 || kWideWaves == 12, "4-, 8- or 12-wave workgroups");
 
 // k-blocks per sub-record of a record with nt tiles
 __host__ __device__ constexpr int wide_g(int nt, int kbh) {
@@ -193,9 +178,7 @@ __device__ __forceinline__ void wide_phase(const WideArgs& a, int& s, int nsub, 
         if (J < nsub) {
             gemm_sub<KBH, NT, J>(bh, bl, (s & 1) ? slot1 : slot0, lane, acc, nkb, bscale);
             NFK_MARK(tr);  // GEMM issued
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            dma_barrier();
             NFK_MARK(tr);  // barrier passed
             wide_stage<KBH, K, INV>(a, s + 2, slot0, slot1, wid, lane);
             ++s;
@@ -228,7 +211,6 @@ __device__ __forceinline__ void knot_phase_w(const f32x4 (&acc)[K / 2], const fl
     }
     return;
 #endif
-#if NFK_WIDE_PK
     // both coordinates' prefixes as packed pairs (bitwise those of the scalar
     // form, nfk_spline.h), then the selects one coordinate at a time
     int pre2[2][K];
@@ -242,19 +224,10 @@ __device__ __forceinline__ void knot_phase_w(const f32x4 (&acc)[K / 2], const fl
         }
         s22 = nfk_prefix_nsf_lean2<K>(u0, u1, l2e, c.m2b, c.fb30, c.mb30, pre2[0], pre2[1]);
     }
-#endif
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-#if NFK_WIDE_PK
         const int(&pre)[K] = pre2[h];
         const float s2 = h ? s22.y : s22.x;
-#else
-        float u[K];
-        int pre[K];
-#pragma unroll
-        for (int p = 0; p < K; ++p) u[p] = acc[p >> 1][2 * h + (p & 1)];
-        const float s2 = nfk_prefix_nsf_lean<K>(u, l2e, c.m2b, c.fb30, c.mb30, pre);
-#endif
         const float lo = __builtin_fmaf(s2, 0.0f, c.lo);  // NaN iff the logits were (knot_phase)
         int p0 = 0, p1 = pre[1 < K ? 1 : 0], k = 0;
         const int xi = __float2int_rd(__builtin_fmaf(xv[h], c.inv30, -c.lo * c.inv30));
@@ -271,7 +244,6 @@ __device__ __forceinline__ void knot_phase_w(const f32x4 (&acc)[K / 2], const fl
         const float e1 = (kk == K - 1) ? c.hi : __builtin_fmaf(c.sp30, (float)p1, lo);
         ek[h] = e;
         sk[h] = e1 - e;
-        if constexpr (K > 8 && !NFK_WIDE_PK) __builtin_amdgcn_sched_barrier(0);  // one coordinate at a time
     }
 }
 
@@ -282,10 +254,8 @@ __device__ __forceinline__ void knot_phase_w(const f32x4 (&acc)[K / 2], const fl
 // whose reloads wait on the frame copies in flight) and every epilogue of a
 // chunk runs back to back.
 __device__ __forceinline__ void wide_pin(int (&kb)[2], float (&e)[2], float (&s)[2]) {
-#if NFK_WIDE_PIN
 #pragma unroll
     for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(kb[h]), "+v"(e[h]), "+v"(s[h]));
-#endif
 }
 
 // Column of a chunk-pair tile: even t = lower coordinate 16 g + t/2, odd t = upper.
@@ -330,8 +300,9 @@ __device__ __forceinline__ void wide_store(const WideArgs& a, const int32_t* m_l
     }
 }
 
+// (one workgroup per CU)
 template <int KBH, int K, bool INV>
-__global__ __launch_bounds__(64 * kWideWaves, kWideWGs) void k_fused_nsf_wide(WideArgs a) {
+__global__ __launch_bounds__(64 * kWideWaves, 1) void k_fused_nsf_wide(WideArgs a) {
     constexpr int HT = 2 * KBH;
     constexpr int NTC = K / 2;  // tiles of a chunk's W, H or D record
     constexpr int S2 = KBH / wide_g(HT, KBH);

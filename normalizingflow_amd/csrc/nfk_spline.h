@@ -12,14 +12,8 @@
 // Python scalars of the reference are, then rounded to fp32 once.
 #pragma once
 
-#ifndef NFK_MAX3_ASM
-#define NFK_MAX3_ASM 1
-#endif
 #include <hip/hip_runtime.h>
 
-#ifndef NFK_TREESUM
-#define NFK_TREESUM 0
-#endif
 #include <stdint.h>
 
 struct NfkSplineConst {
@@ -149,24 +143,14 @@ __device__ __forceinline__ void nfk_knots_nsf_lean(const float (&raw)[K], float 
 // the floored fractions (pre[0] = 0); edge j = fma(span 2^-30, (float)pre[j], lo)
 // for j < K and the pinned right end for j = K.  The fused kernel searches
 // the bin in this integer domain and converts only the two edges it uses.
-// sum of K values: pairwise tree (short dependency chains) or sequential
+// sum of K values, sequential (tried: a pairwise tree for shorter dependency
+// chains, c3 6.28/6.30 vs 6.28/6.28 ms per chain: DESIGN.md section 6)
 template <int K>
 __device__ __forceinline__ float nfk_sum(const float (&v)[K]) {
-#if NFK_TREESUM
-    float t[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) t[i] = v[i];
-#pragma unroll
-    for (int w = 1; w < K; w *= 2)
-#pragma unroll
-        for (int i = 0; i + w < K; i += 2 * w) t[i] = t[i] + t[i + w];
-    return t[0];
-#else
     float s = v[0];
 #pragma unroll
     for (int i = 1; i < K; ++i) s = s + v[i];
     return s;
-#endif
 }
 
 // Returns the second softmax's sum s2 (in [1, K] for finite logits, NaN if a
@@ -191,7 +175,6 @@ __device__ __forceinline__ float nfk_max2(float a, float b) {
 }
 template <int K>
 __device__ __forceinline__ float nfk_max_lean(const float (&raw)[K]) {
-#if NFK_MAX3_ASM
     float t[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) t[i] = raw[i];
@@ -207,12 +190,6 @@ __device__ __forceinline__ float nfk_max_lean(const float (&raw)[K]) {
         n = w;
     }
     return t[0];
-#else
-    float m = raw[0];
-#pragma unroll
-    for (int i = 1; i < K; ++i) m = fmaxf(m, raw[i]);
-    return m;
-#endif
 }
 
 template <int K>
@@ -243,21 +220,10 @@ __device__ __forceinline__ float nfk_prefix_nsf_lean(const float (&raw)[K], floa
 typedef float nfk_f2 __attribute__((ext_vector_type(2)));
 template <int K>
 __device__ __forceinline__ nfk_f2 nfk_sum2(const nfk_f2 (&v)[K]) {
-#if NFK_TREESUM
-    nfk_f2 t[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) t[i] = v[i];
-#pragma unroll
-    for (int w = 1; w < K; w *= 2)
-#pragma unroll
-        for (int i = 0; i + w < K; i += 2 * w) t[i] = t[i] + t[i + w];
-    return t[0];
-#else
     nfk_f2 s = v[0];
 #pragma unroll
     for (int i = 1; i < K; ++i) s = s + v[i];
     return s;
-#endif
 }
 
 template <int K>

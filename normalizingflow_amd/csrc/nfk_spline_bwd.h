@@ -8,9 +8,12 @@
 
 namespace nfk_bwd {
 
-// Diagnostic probes (NFK_BWD_PROBE builds only: tools/dbg_vjp_save.py's
-// "probe" variant): rqs_element_bwd stores its intermediates at fixed slots of
-// a caller array so two evaluations can be compared stage by stage.
+// Diagnostic probes (NFK_BWD_PROBE builds only): rqs_element_bwd stores its
+// intermediates at fixed slots of a caller array so two evaluations can be
+// compared stage by stage.  Its caller (the fused VJP's evaluate-twice
+// diagnostic) is retired; the probes stay because the empty probe loops of a
+// default build still shape the code the compiler emits for nfk_backward.hip,
+// so they go with a change that re-measures that unit.
 #ifdef NFK_BWD_PROBE
 #define NFK_PROBE_PARAM , float* nfk_probe
 #define NFK_PROBE(i, v) (nfk_probe[(i)] = (float)(v))

@@ -55,10 +55,7 @@ constexpr int kWlMaxMT = 8;                    // sample tiles per pass: 128 row
 constexpr int kWlHdr = 64;                     // pack header floats ([0] = 2^-s)
 constexpr float kWlAct = 16384.0f;             // tanh outputs split at 2^14
 constexpr int kWlTarget = 256;                 // GEMM workgroups: at least one per CU
-// the weight stream's loads non-temporal (every weight is read once per layer)
-#ifndef NFK_WL_NT
-#define NFK_WL_NT 1
-#endif
+// (the weight stream's loads are non-temporal: every weight is read once per layer)
 
 int wl_status(const char* what) {
     hipError_t e = hipGetLastError();
@@ -163,13 +160,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_wl_gemm(WlGemm a) {
         for (int t = 0; t < NTW; ++t) {
             const int64_t off = ((int64_t)ntc[t] * a.KB + kb0 + kk) * 2 * 64;
             const f32x4* p = wg + (zoff + live * (off - zoff)) + lane;
-#if NFK_WL_NT
             dst[t][0] = __builtin_nontemporal_load(p);
             dst[t][1] = __builtin_nontemporal_load(p + 64);
-#else
-            dst[t][0] = p[0];
-            dst[t][1] = p[64];
-#endif
         }
     };
 #pragma unroll
@@ -282,13 +274,8 @@ __global__ __launch_bounds__(256, 1) void k_wl_gemm_act(WlGemmAct a) {
         for (int t = 0; t < 2; ++t) {
             const int64_t off = ((int64_t)ntc[t] * a.KB + kb0 + kk) * 2 * 64;
             const f32x4* p = wg + (zoff + live * (off - zoff)) + lane;
-#if NFK_WL_NT
             dw[t][0] = __builtin_nontemporal_load(p);
             dw[t][1] = __builtin_nontemporal_load(p + 64);
-#else
-            dw[t][0] = p[0];
-            dw[t][1] = p[64];
-#endif
         }
 #pragma unroll
         for (int s = 0; s < MT; ++s) {

@@ -33,9 +33,9 @@ def main():
     ap.add_argument("--K", type=int, default=16)
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--c3", action="store_true")
-    ap.add_argument("--slots1", action="store_true", help="c3 kernel built with NFK_NSF_SLOTS=1")
     ap.add_argument("--split", type=int, default=0,
-                    help="c3 kernel in the split form with this many tiles per sub-record (NFK_SPLIT_NS)")
+                    help="c3 kernel in the split form with this many tiles per sub-record "
+                         "(kSplitNs in nfk_fused_impl.h)")
     ap.add_argument("--pipe", action="store_true", help="with --split: the pipelined schedule")
     args = ap.parse_args()
     if args.c3:
@@ -66,7 +66,7 @@ def main():
     cats = []
     ap_pipe = args.pipe
     if args.c3 and args.split and ap_pipe:
-        # pipelined split schedule (NFK_SPLIT_PIPE): every GEMM part is followed
+        # pipelined split schedule (PIPE in k_fused_nsf): every GEMM part is followed
         # by half an epilogue; layer 2 as the plain split form
         cats.append("prologue")
         cats += ["gemm_L1", "bar_gemm", "epi_L1", "bar_epi"]
@@ -88,8 +88,7 @@ def main():
     elif args.c3:
         cats.append("prologue")
         for ph in ["L1", "L2"] + list("ABC") * ((args.size + 15) // 16):
-            cats += (["gemm_" + ph, "bar_gemm", "epi_" + ph, "bar_epi"] if args.slots1
-                     else ["gemm_" + ph, "epi_" + ph, "barrier"])
+            cats += ["gemm_" + ph, "epi_" + ph, "barrier"]
         cats.append("tail")
     elif args.hidden != 256 or args.K != 16 or args.size != 128:
         print("note: categories assume the c5 shape")
