@@ -31,7 +31,7 @@ extern "C" {
 
 typedef void* nfk_stream_t; /* hipStream_t */
 
-#define NFK_ABI_VERSION 3
+#define NFK_ABI_VERSION 4
 #define NFK_EINVAL (-1)
 
 /* status bits, OR-ed into *status by the kernels */
@@ -624,6 +624,75 @@ int nfk_lj_potential_bwd(const float* x, int64_t ldx, const float* g, float* gx,
                          int64_t batch, int32_t n, int32_t dim, double boxlength, double sigma,
                          double epsilon, int32_t has_cutoff, double cutoff, int32_t shift,
                          nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Dynamics of the three systems, nfk_dynamics.hip: integration_step
+ * (systems.py:297-338, 382-401) for a batch of independent trajectories in ONE
+ * launch, and the Metropolis step of HMC (nf/hmc.py:56-63).
+ *
+ * x_in, v_in [batch, W] (row strides ldxi, ldvi; W = natoms*dim, npart*dim or
+ * n*dim) -> x_out, v_out (ldxo, ldvo; x_out may be x_in and v_out may be v_in,
+ * with the same stride) and pot_out [batch], the potential at x_out: -log_prob
+ * for the Einstein crystal and the mixture, the energy for Lennard-Jones, with
+ * the arithmetic of nfk_einstein_logprob (its scalar form) / nfk_gmix_logprob /
+ * nfk_lj_potential.  All fp32, no contraction.  dt and dt_sq are the
+ * reference's Python scalars dt and dt**2, rounded to fp32 once on the host.
+ * With G = F(x_in), per step, path_len (>= 0) times, in this order:
+ *   x' = (x + v*dt) + (G*0.5f)*dt_sq
+ *   Gn = F(scheme ? x' : x)
+ *   v' = v + (dt*(G + Gn))*0.5f;   x = x', v = v', G = Gn
+ * scheme 0 is the reference's integrator, which evaluates the "new" force at
+ * the OLD position (G_k = F(x_{k-1}): not time-reversible); scheme 1 is
+ * velocity Verlet (G_k = F(x_k)).  path_len = 0 copies x and v and returns the
+ * potential.  F = -dU/dx is the expression of the system's backward entry
+ * point at g = 1, the same device functions in the same order: d log_prob/dx
+ * of nfk_einstein_logprob_bwd / nfk_gmix_logprob_bwd, the negated gx of
+ * nfk_lj_potential_bwd.  So a launch equals, bit for bit in x and v, the chain
+ * of those kernels and elementwise fp32 ops it replaces.  NaN and inf
+ * propagate as they do there; there is no status word.
+ * x, v and the current force stay in registers across the step loop (a
+ * wave-uniform runtime bound).  Einstein: a lane per coordinate; mixture: a
+ * lane per particle (both forces act on their own coordinate / particle alone,
+ * so a lane finishes one trajectory and takes the next, lanes_for(W) further
+ * on); the row potential is the fixed-order group sum of the log-density
+ * kernels.  Lennard-Jones: nfk_lj_potential's mapping (a row on next_pow2(n)
+ * lanes for n <= 64, a wave with up to 4 particles per lane for n <= 256);
+ * every step re-stages the row's positions in LDS as float4 and the j loop
+ * reads them by broadcast; two LDS buffers per row (<= 32 KiB per block) leave
+ * one barrier per step.  Grid-stride over rows with the grid caps of the
+ * kernels they follow.
+ * The system constants are those of nfk_einstein_logprob / nfk_gmix_logprob /
+ * nfk_lj_potential, and so are the supported shapes (nfk_gmix_supported,
+ * nfk_lj_supported).  scheme outside {0, 1}, path_len < 0, a leading dimension
+ * below W or an unsupported shape: NFK_EINVAL, and nothing is launched.
+ * ------------------------------------------------------------------------- */
+int nfk_einstein_trajectory(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi,
+                            float* x_out, int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out,
+                            int64_t batch, int32_t path_len, double dt, double dt_sq, int32_t scheme,
+                            const float* centers, int32_t natoms, int32_t dim, float scale,
+                            float half_log_det, int32_t has_box, double boxlength, nfk_stream_t stream);
+int nfk_gmix_trajectory(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi,
+                        float* x_out, int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out,
+                        int64_t batch, int32_t path_len, double dt, double dt_sq, int32_t scheme,
+                        const float* centers, const float* scales, const float* hlds, int32_t npart,
+                        int32_t dim, int32_t ncenters, nfk_stream_t stream);
+int nfk_lj_trajectory(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out,
+                      int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out, int64_t batch,
+                      int32_t path_len, double dt, double dt_sq, int32_t scheme, int32_t n, int32_t dim,
+                      double boxlength, double sigma, double epsilon, int32_t has_cutoff, double cutoff,
+                      int32_t shift, nfk_stream_t stream);
+/* nfk_hmc_accept: chain c of `chains` accepts its proposal when
+ *   r[c] < expf(((u_cur[c] - u_new[c]) [+ k_cur[c]) - k_new[c]] * (float)beta)
+ * (accurate expf; k_cur and k_new are both null -- the reference's
+ * potential-only test -- or both given; a NaN exponent compares false: a
+ * rejection).  On acceptance x_cur[c, :width] = x_new[c, :width],
+ * u_cur[c] = u_new[c] and naccept[c] += 1 (int32, nullable); a rejected chain
+ * is left as it is.  x_cur (row stride ldc) and x_new (ldn) do not overlap.  A
+ * chain takes next_pow2(width) <= 64 lanes whose first lane decides; all
+ * writes are ordinary vector stores. */
+int nfk_hmc_accept(float* x_cur, int64_t ldc, const float* x_new, int64_t ldn, float* u_cur,
+                   const float* u_new, const float* k_cur, const float* k_new, const float* r,
+                   int32_t* naccept, int64_t chains, int32_t width, double beta, nfk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NFK_LIBRARY", os.path.join(_HERE, "libnfk.so"))
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 NFK_EINVAL = -1
 ST_INSIDE_SEEN = 1
@@ -191,6 +191,24 @@ SIGNATURES = {
         P, I64, P, P, I64,              # x, ldx, g, gx, ldgx
         I64, I32, I32,                  # batch, n, dim
         F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_einstein_trajectory": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, F64, F64, I32,        # batch, path_len, dt, dt_sq, scheme
+        P, I32, I32, F32, F32,          # centers, natoms, dim, scale, half_log_det
+        I32, F64, P]),                  # has_box, boxlength, stream
+    "nfk_gmix_trajectory": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, F64, F64, I32,        # batch, path_len, dt, dt_sq, scheme
+        P, P, P, I32, I32, I32, P]),    # centers, scales, hlds, npart, dim, ncenters, stream
+    "nfk_lj_trajectory": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, F64, F64, I32,        # batch, path_len, dt, dt_sq, scheme
+        I32, I32,                       # n, dim
+        F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_hmc_accept": (ctypes.c_int, [
+        P, I64, P, I64, P, P,           # x_cur, ldc, x_new, ldn, u_cur, u_new
+        P, P, P, P,                     # k_cur, k_new, r, naccept
+        I64, I32, F64, P]),             # chains, width, beta, stream
 }
 
 _lock = threading.Lock()

@@ -15,6 +15,9 @@ restated for the flow path.
 * ``reverse_kl`` / ``forward_kl`` -- the losses of setup.py:90-100;
   ``q_matrix`` -- the Q matrix of test.py:33-50 (generate_from_nf, evaluate
   and the target's energies), up to ``Q = torch.stack(...)``.
+* ``collect_hmc_data`` / ``integrate_out_v`` / ``relaxation_step`` -- the
+  dynamics of applications/src/dynamics.py over systems.py's own integrators
+  (no LAMMPS), every trajectory of a call in one launch.
 * ``save_checkpoint`` / ``load_checkpoint`` -- the checkpoint dict of
   train.py:39-40 and the loader of setup.py:102-109 (``load_state_dict``
   with ``strict=False``), read with ``torch.load(weights_only=True)``.
@@ -29,11 +32,13 @@ import yaml
 
 from . import flows as F_
 from . import systems
+from .hmc import HMC
 from .models import NormalizingFlowModel
 
 __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flows", "build_prior",
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
-           "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix"]
+           "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
+           "integrate_out_v", "relaxation_step"]
 
 
 class CfgNode(dict):
@@ -278,3 +283,53 @@ def q_matrix(cfg, model, potential, nsamples, batchsize=500):
     q11 = -(potential.potential(traj1.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(q00.device)
     Q1 = torch.transpose(torch.vstack((q10, q11)), 0, 1)
     return torch.stack((Q0, Q1))
+
+
+def _sim_positions(simulation, rows, dim):
+    """[B, W] rows in the shape the simulation holds positions in (LJ: [B, n, dim])."""
+    if isinstance(simulation, systems.LJ):
+        return rows.reshape(rows.shape[0], -1, dim)
+    return rows
+
+
+def collect_hmc_data(cfg, model, hmc, burnin=100, epochs=500):
+    """dynamics.py:59-65 without the file writes: one model sample relaxed by
+    ``epochs`` HMC moves; returns (traj[burnin:], acceptance rate)."""
+    samples, _, _ = model.sample(1)
+    init = _sim_positions(hmc.simulation, samples.detach().reshape(1, -1), hmc.dim)[0]
+    traj, _, _, acc_prob = hmc.hmc(epochs=epochs, init_pos=init)
+    return traj[burnin:], acc_prob
+
+
+def integrate_out_v(model, hmc, frames, npoints=10):
+    """dynamics.py:26-36 for every row of ``frames`` [F, W] at once: npoints
+    velocity draws per frame, all F * npoints trajectories in one launch, one
+    ``model.evaluate``, then logsumexp over a frame's draws - log(npoints): [F]
+    (a 1-D frame gives a scalar, as the reference does)."""
+    rows = frames.detach().reshape(1, -1) if frames.dim() == 1 else frames.detach().reshape(len(frames), -1)
+    start = rows.repeat_interleave(npoints, dim=0)  # frame-major: a frame's draws are consecutive
+    hmc.simulation.set_position(_sim_positions(hmc.simulation, start, hmc.dim))
+    v, _ = hmc.generate_v()
+    position, _, _ = hmc.run_sim(v)
+    q_nf = model.evaluate(position.reshape(start.shape).float())
+    out = torch.logsumexp(q_nf.reshape(rows.shape[0], npoints), 1) - torch.log(torch.tensor(float(npoints)))
+    return out[0] if frames.dim() == 1 else out
+
+
+def relaxation_step(cfg, model, simulation, traj, path_len=12, beta=None, init_beta=None, mass=None,
+                    npoints=10):
+    """dynamics.py:38-56 in its generic form (``simulation`` is one of
+    systems.py's classes): one HMC trajectory of ``path_len`` steps per row of
+    ``traj``, all in one launch, then ``integrate_out_v`` of the relaxed frames.
+    Returns (traj_new, q_learned, -U_new / kT) on ``cfg.device``.  ``beta``
+    defaults to 1 / cfg.dataset.kT."""
+    kT = cfg.dataset.kT
+    run = HMC(simulation, beta=1 / kT if beta is None else beta, mass=mass, path_len=path_len,
+              init_beta=init_beta, dim=cfg.dataset.dim)
+    rows = traj.detach().reshape(len(traj), -1)
+    simulation.set_position(_sim_positions(simulation, rows, cfg.dataset.dim))
+    position, potential, _ = run.run_sim()
+    traj_new = position.reshape(rows.shape)
+    q_learned = integrate_out_v(model, run, traj_new, npoints)
+    return (traj_new.float().to(cfg.device), q_learned.to(cfg.device),
+            (-potential.reshape(-1) / kT).to(cfg.device))

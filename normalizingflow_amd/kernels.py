@@ -560,6 +560,68 @@ def lj_potential_bwd(x, g, gx, *, n, dim, boxlength, sigma=1.0, epsilon=1.0, cut
            n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
 
 
+# ---------------------------------------------------------------------------
+# trajectories and the Metropolis step (nfk_dynamics.hip)
+def _traj_args(x_in, v_in, x_out, v_out, pot, width, path_len, dt, scheme):
+    B = x_in.shape[0]
+    mats = []
+    for t, name in ((x_in, "x_in"), (v_in, "v_in"), (x_out, "x_out"), (v_out, "v_out")):
+        if t.dim() != 2 or t.shape != (B, width):
+            raise ValueError("%s must be [%d, %d], got %s" % (name, B, width, tuple(t.shape)))
+        mats.extend(_mat(t, name))
+    if scheme not in (0, 1):
+        raise ValueError("scheme must be 0 (the reference's lagged force) or 1 (velocity Verlet)")
+    dt = float(dt)
+    return (*mats, _vec(pot, B, "pot"), B, int(path_len), dt, dt ** 2, int(scheme))
+
+
+def einstein_trajectory(x_in, v_in, x_out, v_out, pot, centers, *, path_len, dt, scheme, scale, hld,
+                        boxlength=None):
+    """nfk_einstein_trajectory: path_len integrator steps of every row in one
+    launch.  ``x_out`` / ``v_out`` may be ``x_in`` / ``v_in``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, centers)
+    natoms, dim = centers.shape
+    has_box, L = _box(boxlength)
+    _timed("nfk_einstein_trajectory", dev, "nfk_einstein_trajectory",
+           *_traj_args(x_in, v_in, x_out, v_out, pot, natoms * dim, path_len, dt, scheme),
+           _vec(centers, natoms * dim, "centers"), natoms, dim, float(scale), float(hld), has_box, L,
+           _stream(dev))
+
+
+def gmix_trajectory(x_in, v_in, x_out, v_out, pot, centers, scales, hlds, *, path_len, dt, scheme, npart):
+    """nfk_gmix_trajectory."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, centers, scales, hlds)
+    M, dim = centers.shape
+    _timed("nfk_gmix_trajectory", dev, "nfk_gmix_trajectory",
+           *_traj_args(x_in, v_in, x_out, v_out, pot, int(npart) * dim, path_len, dt, scheme),
+           _vec(centers, M * dim, "centers"), _vec(scales, M, "scales"), _vec(hlds, M, "hlds"), int(npart),
+           dim, M, _stream(dev))
+
+
+def lj_trajectory(x_in, v_in, x_out, v_out, pot, *, path_len, dt, scheme, n, dim, boxlength, sigma=1.0,
+                  epsilon=1.0, cutoff=None, shift=True):
+    """nfk_lj_trajectory.  Rows are [n*dim]."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot)
+    _timed("nfk_lj_trajectory", dev, "nfk_lj_trajectory",
+           *_traj_args(x_in, v_in, x_out, v_out, pot, n * dim, path_len, dt, scheme), n, dim,
+           *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
+
+
+def hmc_accept(x_cur, x_new, u_cur, u_new, r, naccept, *, beta, k_cur=None, k_new=None):
+    """nfk_hmc_accept: the Metropolis step over the rows of x_cur, in place."""
+    dev = _require_hip(x_cur, x_new, u_cur, u_new, r, naccept, k_cur, k_new)
+    C, W = x_cur.shape
+    if x_new.shape != x_cur.shape:
+        raise ValueError("x_new must be %s, got %s" % (tuple(x_cur.shape), tuple(x_new.shape)))
+    if (k_cur is None) != (k_new is None):
+        raise ValueError("k_cur and k_new come together")
+    cp, ldc = _mat(x_cur, "x_cur")
+    np_, ldn = _mat(x_new, "x_new")
+    _timed("nfk_hmc_accept", dev, "nfk_hmc_accept", cp, ldc, np_, ldn, _vec(u_cur, C, "u_cur"),
+           _vec(u_new, C, "u_new"), _vec(k_cur, C, "k_cur"), _vec(k_new, C, "k_new"), _vec(r, C, "r"),
+           _vec(naccept, C, "naccept", torch.int32), C, W, float(beta), _stream(dev))
+
+
 def trig_features(x, feat, B):
     dev = _require_hip(x, feat)
     n_rows, n = x.shape

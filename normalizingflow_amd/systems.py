@@ -3,7 +3,9 @@
 the reference's constructor signatures and method names.
 
 fp32 tensors on the HIP device take the kernels of nfk_systems.hip (one launch
-per log_prob / potential, one per backward; no [B, N, N] temporary for LJ).
+per log_prob / potential, one per backward; no [B, N, N] temporary for LJ)
+and, for ``integration_step``, of nfk_dynamics.hip (a whole batch of
+trajectories in one launch).
 Every other input -- CPU tensors, other float dtypes, parameters that require
 grad, shapes the kernels do not take -- runs the plain-torch restatement in
 this module: the same formulas in the input's dtype, differentiable by
@@ -15,8 +17,8 @@ what the Normal prior gets: the kernel with ``+ sign * log|det|`` fused, a
 status word for the reference's NaN ``ValueError``, an autograd node under
 training and HIP-graph capture (models._prior_log_prob).
 
-Out of scope: LAMMPS, Fe, the MD integrators (integration_step,
-set_position, ...), HMC, the MBAR/BAR solvers and plotting.
+Out of scope: LAMMPS, Fe, the MBAR/BAR solvers and plotting.  HMC is in
+hmc.py.
 """
 from __future__ import annotations
 
@@ -103,7 +105,132 @@ def _raise_nan(x, who):
                          % type(who).__name__)
 
 
-class _KernelBacked:
+_SCHEMES = {"reference": 0, "verlet": 1}
+
+
+class _Dynamics:
+    """The state and the integrator of systems.py:297-338 and 382-401, batched:
+    ``set_position`` / ``set_velocity`` / ``get_position`` / ``get_velocity`` /
+    ``get_potential`` and ``integration_step``.
+
+    A position is one configuration or a batch of independent ones, [W] or
+    [B, W] (``LJ``: [..., n, dim]).  The reference's own batch, one flattened
+    vector of B configurations, gives the same numbers; results come back in
+    the shape that was given, the potential as [B].
+
+    ``scheme="reference"`` is the reference's integrator, which evaluates the
+    "new" force at the old position (G_k = F(x_{k-1})) and is therefore not
+    time-reversible; ``scheme="verlet"`` is velocity Verlet (G_k = F(x_k)).
+    Per step, in the input's dtype and in this order:
+
+        x' = (x + v*dt) + (G*0.5)*dt**2
+        Gn = F(x' if verlet else x)
+        v' = v + (dt*(G + Gn))*0.5
+
+    fp32 device tensors at the kernels' shapes take ONE launch for the whole
+    trajectory (nfk_dynamics.hip), bit for bit the per-step path in x and v.
+    Everything else -- CPU, fp64, other shapes, ``use_kernels = False`` or
+    ``fused_dynamics = False`` -- runs the per-step path: ``get_force`` /
+    ``force`` per step plus torch elementwise ops.
+
+    Two deliberate differences from the reference.  Its ``self.force = ...``
+    replaces ``GaussianMixture.force``, the method, by a tensor; here the last
+    force is ``self.last_force`` and ``force`` stays callable.  And its outputs
+    carry an autograd graph that grows by one force evaluation per step; here
+    both paths return detached tensors (``get_force`` keeps the
+    ``create_graph=True`` spelling)."""
+
+    fused_dynamics = True
+    position = None
+    velocity = None
+    _last_force = None
+    _replay = None
+
+    def set_position(self, position):
+        self.position = position
+
+    def get_position(self):
+        return self.position
+
+    def set_velocity(self, velocity):
+        self.velocity = velocity
+
+    def get_velocity(self):
+        return self.velocity
+
+    def get_potential(self, x=None):
+        return self.potential(self.position if x is None else x)
+
+    @property
+    def last_force(self):
+        """G after the last ``integration_step``.  The fused launch keeps the
+        force in registers, so after one it is evaluated on the first read
+        (for the reference scheme at x_{k-1}, reached by one more launch from
+        the tensors the step started from)."""
+        if self._last_force is None and self._replay is not None:
+            x, v, path_len, dt, sch = self._replay
+            if sch == 0 and path_len > 0:
+                x = self._integrate(x, v, path_len - 1, dt, sch)[0]
+            elif path_len > 0:
+                x = self.position
+            self._last_force = self._force_detached(x)
+        return self._last_force
+
+    def _force_detached(self, x):
+        with torch.enable_grad():
+            return self.get_force(x.detach()).detach()
+
+    def _dyn_fused_ok(self, x, v):
+        return (self.fused_dynamics and torch.is_tensor(v) and v.dtype == x.dtype and v.device == x.device
+                and self._kernel_ok(x))
+
+    def _integrate(self, x, v, path_len, dt, sch, keep_force=False):
+        """(x, v, potential) after path_len steps; x, v in one shape."""
+        if self._dyn_fused_ok(x, v):
+            xr, vr = self._dyn_rows(x), self._dyn_rows(v)
+            xo, vo = torch.empty_like(xr, memory_format=torch.contiguous_format), torch.empty_like(
+                vr, memory_format=torch.contiguous_format)
+            pot = torch.empty(xr.shape[0], dtype=torch.float32, device=xr.device)
+            self._trajectory(xr.detach(), vr.detach(), xo, vo, pot, path_len, dt, sch)
+            if keep_force:
+                self._last_force, self._replay = None, (x, v, path_len, dt, sch)
+            return xo.reshape(x.shape), vo.reshape(x.shape), self._dyn_pot_shape(pot, x)
+        x, v = x.detach(), v.detach()
+        G = self._force_detached(x)
+        for _ in range(path_len):
+            xn = (x + v * dt) + (G * 0.5) * dt ** 2
+            Gn = self._force_detached(xn if sch else x)
+            v = v + (dt * (G + Gn)) * 0.5
+            x, G = xn, Gn
+        if keep_force:
+            self._last_force, self._replay = G, None
+        with torch.no_grad():
+            return x, v, self.potential(x)
+
+    def integration_step(self, path_len=1, dt=0.005, init_pos=None, init_velocity=None, scheme="reference"):
+        """``path_len`` steps of ``dt`` (None: 0.005) from the held position and
+        velocity (or ``init_pos`` / ``init_velocity``); returns (position,
+        potential) as the reference does and holds the final state in
+        ``self.position`` / ``self.velocity``."""
+        if scheme not in _SCHEMES:
+            raise ValueError("scheme must be 'reference' or 'verlet', got %r" % (scheme,))
+        if init_pos is not None:
+            self.set_position(init_pos)
+        if init_velocity is not None:
+            self.set_velocity(init_velocity)
+        if dt is None:
+            dt = 0.005
+        path_len = int(path_len)
+        if path_len < 0:
+            raise ValueError("path_len must be >= 0")
+        x = self.position
+        x, v, pot = self._integrate(x, self.velocity.reshape(x.shape), path_len, dt, _SCHEMES[scheme],
+                                    keep_force=True)
+        self.position, self.velocity = x, v
+        return x, pot
+
+
+class _KernelBacked(_Dynamics):
     """Shared dispatch: ``use_kernels = False`` on an object forces its torch path."""
 
     use_kernels = True
@@ -139,6 +266,12 @@ class _KernelBacked:
         x.requires_grad_()
         pot = self.potential(x)
         return -torch.autograd.grad(pot, x, torch.ones_like(pot), create_graph=True)[0]
+
+    def _dyn_rows(self, t):
+        return _rows(t, self.width)
+
+    def _dyn_pot_shape(self, pot, x):
+        return pot
 
 
 # ---------------------------------------------------------------------------
@@ -208,6 +341,15 @@ class EinsteinCrystal(_KernelBacked):
         scale, hld = self._consts()
         K_.einstein_logprob(z, self.centers, out, scale=scale, hld=hld, boxlength=self.boxlength,
                             logdet=logdet, sign=sign, status=status)
+
+    @property
+    def nparticles(self):
+        return self.natoms
+
+    def _trajectory(self, x, v, xo, vo, pot, path_len, dt, sch):
+        scale, hld = self._consts()
+        K_.einstein_trajectory(x, v, xo, vo, pot, self.centers, path_len=path_len, dt=dt, scheme=sch,
+                               scale=scale, hld=hld, boxlength=self.boxlength)
 
     def _log_prob_torch(self, x):
         if self._validate_args:
@@ -326,11 +468,13 @@ class GaussianMixture(_KernelBacked):
             prob = prob + 1 / self.ncenters * torch.exp(lp)
         return torch.sum(torch.log(prob).reshape(-1, self.nparticles), dim=1)
 
-    def get_potential(self, x):
-        return self.potential(x)
-
     def force(self, x):
         return self.get_force(x)
+
+    def _trajectory(self, x, v, xo, vo, pot, path_len, dt, sch):
+        scales, hlds = self._consts()
+        K_.gmix_trajectory(x, v, xo, vo, pot, self.centers, scales, hlds, path_len=path_len, dt=dt,
+                           scheme=sch, npart=self.nparticles)
 
     def sample(self, nsamples, flatten=True):
         with torch.no_grad():
@@ -368,7 +512,7 @@ class _LJFn(torch.autograd.Function):
         return gx, None, None, None
 
 
-class LJ:
+class LJ(_Dynamics):
     """systems.py:144-189: Lennard-Jones particles in a periodic cubic box,
     plus the trajectory holder of SimData (``sample``).  ``pos_dir`` may be a
     tensor, a ``.npy`` / ``.pt`` path or an XYZ file.
@@ -456,6 +600,34 @@ class LJ:
             x = particle_pos.detach().requires_grad_()
             pot = self.potential(x)
             return -torch.autograd.grad(pot, x, torch.ones_like(pot))[0]
+
+    @property
+    def nparticles(self):
+        """Read from the held position: LJ stores no particle count."""
+        if self.position is None:
+            raise AttributeError("LJ.nparticles needs a position: call set_position first")
+        return self.position.shape[-2]
+
+    def get_force(self, x):
+        return self.force(x)
+
+    def _dyn_rows(self, t):
+        return _rows(t, t.shape[-2] * t.shape[-1])
+
+    def _dyn_pot_shape(self, pot, x):
+        return pot.reshape(x.shape[:-2])
+
+    def _trajectory(self, x, v, xo, vo, pot, path_len, dt, sch):
+        n, dim = self._traj_nd  # the rows are [n*dim]: _integrate notes the split
+        K_.lj_trajectory(x, v, xo, vo, pot, path_len=path_len, dt=dt, scheme=sch, n=n, dim=dim, **self._kw())
+
+    def _integrate(self, x, v, path_len, dt, sch, keep_force=False):
+        if x.dim() < 2:
+            raise ValueError("LJ positions are [..., n, dim]; got shape %s" % (tuple(x.shape),))
+        if self.boxlength is None:
+            raise TypeError("unsupported operand type(s) for *: 'float' and 'NoneType' (boxlength=None)")
+        self._traj_nd = tuple(x.shape[-2:])
+        return super()._integrate(x, v, path_len, dt, sch, keep_force)
 
     def sample(self, nsamples, flatten=True, random=True):
         if random:
