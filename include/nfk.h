@@ -694,6 +694,47 @@ int nfk_hmc_accept(float* x_cur, int64_t ldc, const float* x_new, int64_t ldn, f
                    const float* u_new, const float* k_cur, const float* k_new, const float* r,
                    int32_t* naccept, int64_t chains, int32_t width, double beta, nfk_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Bennett acceptance ratio (applications/src/bar.py:16-68), `problems`
+ * independent solves in one launch, and the exponential averages of
+ * test.py:67-68.  Problem p works on wf_i = w_f[idx_f ? idx_f[p*ldif + i] : i],
+ * i < n_f, and wr_i likewise (int32 row gathers, e.g. bootstrap resamples; both
+ * null: the plain vectors).  Inputs are fp32, promoted once; all arithmetic is
+ * fp64 without contraction.  With M = log(n_f / n_r) and
+ * g(a) = -log(1 + e^a), one iteration maps D to
+ *   D' = [LSE_i(g(M - wr_i - D) - wr_i) - log n_r] - [LSE_i g(M + wf_i - D) - log n_f]
+ * (LSE: max-shifted log-sum-exp; the largest term of either sum is that of the
+ * smallest work value, g being non-increasing, so the max pass runs once over
+ * the work values and an iteration is one sum pass), starting at delta0.
+ * After iteration k
+ * (0-based) rc = |(D' - D) / D'|; the loop stops when k > 0 && rc < rtol, or
+ * k + 1 == max_iterations, so rtol = 0 returns exactly the max_iterations-th
+ * iterate.  iters[p] = iterations done, out[p*3] = the last D',
+ * out[p*3+1] = log mean_i exp(wf_i), out[p*3+2] = log mean_i exp(wr_i) (both
+ * max-shifted).
+ * Deviations from the reference's text: (1) g is evaluated as
+ * -(max(a,0) + log1p(exp(-|a|))), finite for every finite a (the reference's
+ * form shifts by min(a,0) and overflows for |a| >~ 709; same function,
+ * rounding apart); (2) a NaN D' ends the loop at once and is returned (the
+ * reference spins to maximum_iterations and returns the same NaN); (3) every
+ * loop exit compares one LDS word read by all lanes: the trip count is
+ * workgroup-uniform and bounded by max_iterations.
+ * One workgroup per problem (256, 512 or 1024 threads by n_f + n_r alone;
+ * grid-stride above 4096 problems), no atomics.  n_f + n_r <= nfk_bar_stage_cap(): the work values are gathered
+ * once into LDS (fp32) and every pass reads them there; otherwise every pass
+ * re-reads them from global memory through the index rows.  Both forms give a
+ * lane the same elements in the same order and share one reduction tree: same
+ * bits, and two runs are bitwise equal.  Index values are not validated.
+ * NFK_EINVAL, nothing launched: n_f < 1, n_r < 1, problems < 1,
+ * max_iterations < 1, rtol < 0 or NaN, a leading dimension below its row
+ * length, null w_f / w_r / out / iters, exactly one of idx_f / idx_r when
+ * problems > 1.
+ * ------------------------------------------------------------------------- */
+int nfk_bar_stage_cap(void); /* host-only: largest n_f + n_r kept in LDS */
+int nfk_bar(const float* w_f, int64_t n_f, const float* w_r, int64_t n_r, const int32_t* idx_f,
+            int64_t ldif, const int32_t* idx_r, int64_t ldir, int64_t problems, double delta0,
+            int32_t max_iterations, double rtol, double* out, int32_t* iters, nfk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

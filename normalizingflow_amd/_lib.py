@@ -209,6 +209,12 @@ SIGNATURES = {
         P, I64, P, I64, P, P,           # x_cur, ldc, x_new, ldn, u_cur, u_new
         P, P, P, P,                     # k_cur, k_new, r, naccept
         I64, I32, F64, P]),             # chains, width, beta, stream
+    "nfk_bar_stage_cap": (ctypes.c_int, []),
+    "nfk_bar": (ctypes.c_int, [
+        P, I64, P, I64,                 # w_f, n_f, w_r, n_r
+        P, I64, P, I64,                 # idx_f, ldif, idx_r, ldir
+        I64, F64, I32, F64,             # problems, delta0, max_iterations, rtol
+        P, P, P]),                      # out, iters, stream
 }
 
 _lock = threading.Lock()

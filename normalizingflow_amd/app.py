@@ -14,7 +14,11 @@ restated for the flow path.
   are out of scope.
 * ``reverse_kl`` / ``forward_kl`` -- the losses of setup.py:90-100;
   ``q_matrix`` -- the Q matrix of test.py:33-50 (generate_from_nf, evaluate
-  and the target's energies), up to ``Q = torch.stack(...)``.
+  and the target's energies), up to ``Q = torch.stack(...)``;
+  ``q_matrix_relaxed`` -- the same through ``relaxation_step``.
+* ``fe_estimates`` / ``fe_diff`` -- the free-energy estimates of test.py:55-68
+  (BAR and the two exponential averages) over bar.py's batched solver, with
+  bootstrap errors; Q never leaves its device.
 * ``collect_hmc_data`` / ``integrate_out_v`` / ``relaxation_step`` -- the
   dynamics of applications/src/dynamics.py over systems.py's own integrators
   (no LAMMPS), every trajectory of a call in one launch.
@@ -30,6 +34,7 @@ import copy
 import torch
 import yaml
 
+from . import bar as bar_
 from . import flows as F_
 from . import systems
 from .hmc import HMC
@@ -38,7 +43,7 @@ from .models import NormalizingFlowModel
 __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flows", "build_prior",
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
            "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
-           "integrate_out_v", "relaxation_step"]
+           "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff"]
 
 
 class CfgNode(dict):
@@ -271,7 +276,8 @@ def evaluate(model, x, batchsize=50):
 def q_matrix(cfg, model, potential, nsamples, batchsize=500):
     """The [2, nsamples, 2] tensor Q of test.py:34-50 without relaxation:
     Q[0] = (log q, -U/kT) of flow samples, Q[1] = the same of target samples.
-    The energies stay on the device; nothing is written and no solver runs."""
+    The energies stay on the device and nothing is written; ``fe_estimates``
+    turns Q into free-energy estimates."""
     d = cfg.dataset
     traj0, q00 = generate_from_nf(model, nsamples, batchsize=batchsize)
     q01 = -(potential.potential(traj0.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(q00.device)
@@ -333,3 +339,69 @@ def relaxation_step(cfg, model, simulation, traj, path_len=12, beta=None, init_b
     q_learned = integrate_out_v(model, run, traj_new, npoints)
     return (traj_new.float().to(cfg.device), q_learned.to(cfg.device),
             (-potential.reshape(-1) / kT).to(cfg.device))
+
+
+def q_matrix_relaxed(cfg, model, potential, nsamples, batchsize=500, **relaxation_kw):
+    """The Q of test.py:34-50 with ``relaxation=True``: the flow's samples and
+    the target's each go through ``relaxation_step`` (test.py:35-36, 41-42),
+    whose keyword arguments ``relaxation_kw`` are."""
+    traj0, _ = generate_from_nf(model, nsamples, batchsize=batchsize)
+    _, q00, q01 = relaxation_step(cfg, model, potential, traj0, **relaxation_kw)
+    traj1 = potential.sample(nsamples)
+    _, q10, q11 = relaxation_step(cfg, model, potential, traj1, **relaxation_kw)
+    Q0 = torch.transpose(torch.vstack((q00, q01)), 0, 1)
+    Q1 = torch.transpose(torch.vstack((q10, q11)), 0, 1)
+    return torch.stack((Q0, Q1)).detach()
+
+
+def fe_estimates(cfg, Q, nboot=0, generator=None):
+    """test.py:55-68 from a [2, N, 2] Q on any device: the offsets
+    ``to_subtract_0/1`` (the minima of Q[1]'s columns), the work values
+    ``w_F = Q[0,:,0] - Q[0,:,1]`` and ``w_R = -Q[1,:,0] + Q[1,:,1]`` of the
+    shifted Q in Q's dtype, and with off = to_subtract_0 - to_subtract_1
+
+        bar = (off + DeltaF) / nparticles * kT      (DeltaF: bar.BAR(w_F, w_R))
+        md  = (off - log mean exp(w_R)) / nparticles * kT
+        nf  = (off + log mean exp(w_F)) / nparticles * kT
+
+    as 0-d fp64 tensors on Q's device; nothing synchronises.  With ``nboot`` > 0
+    the bootstrap standard deviations ``(bar_err, md_err, nf_err)`` follow
+    (``nboot`` resamples of w_F and w_R, ``bar.bootstrap``).  Q is not modified
+    (the reference shifts it in place).  ``emus`` (test.py:61-63) and the MBAR
+    error (test.py:70) are not restated: their solver is a private package."""
+    d = cfg.dataset
+    Q = Q.detach()
+    if Q.dim() != 3 or Q.shape[0] != 2 or Q.shape[2] != 2:
+        raise ValueError("Q must be [2, N, 2], got %s" % (tuple(Q.shape),))
+    to_subtract = torch.stack((torch.min(Q[1][:, 0]), torch.min(Q[1][:, 1])))
+    Qs = Q - to_subtract
+    w_F = Qs[0][:, 0] - Qs[0][:, 1]
+    w_R = -Qs[1][:, 0] + Qs[1][:, 1]
+    off = (to_subtract[0] - to_subtract[1]).double()
+
+    def scaled(o):
+        return tuple((off + sgn * o[..., j]) / d.nparticles * d.kT for j, sgn in ((0, 1.0), (2, -1.0), (1, 1.0)))
+
+    out, _ = bar_.bar_solve(w_F, w_R)
+    est = scaled(out[0])
+    if not nboot:
+        return est
+    boot = scaled(bar_.bootstrap(w_F, w_R, nboot, generator=generator))
+    return est + tuple(b.std() for b in boot)
+
+
+def fe_diff(cfg, model, potential, nsamples, relaxation=False, return_err=False, nboot=200, batchsize=500,
+            *, generator=None, relaxation_kw=None):
+    """test.py:33-72: ``(bar, md, nf)`` free-energy differences per particle
+    between the flow and its target from ``nsamples`` samples of each
+    (``relaxation=True``: both relaxed by ``relaxation_step`` first, called with
+    ``relaxation_kw``).  ``return_err=True`` appends the bootstrap standard
+    deviations ``(bar_err, md_err, nf_err)`` over ``nboot`` resamples.  Every
+    result is a 0-d fp64 tensor on the model's device.  No file is written and
+    nothing is plotted; ``emus`` and the MBAR error of test.py:61-63, 70 are not
+    restated (see ``fe_estimates``)."""
+    if relaxation:
+        Q = q_matrix_relaxed(cfg, model, potential, nsamples, batchsize=batchsize, **(relaxation_kw or {}))
+    else:
+        Q = q_matrix(cfg, model, potential, nsamples, batchsize=batchsize)
+    return fe_estimates(cfg, Q, nboot=nboot if return_err else 0, generator=generator)

@@ -622,6 +622,41 @@ def hmc_accept(x_cur, x_new, u_cur, u_new, r, naccept, *, beta, k_cur=None, k_ne
            _vec(naccept, C, "naccept", torch.int32), C, W, float(beta), _stream(dev))
 
 
+def bar_stage_cap():
+    """Largest n_f + n_r whose work values nfk_bar keeps in LDS."""
+    return int(_lib.load().nfk_bar_stage_cap())
+
+
+def _idx_rows(t, P, n, name):
+    """(ptr, row stride) of a [P, n] int32 index matrix with unit column stride."""
+    if t is None:
+        return None, 0
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape != (P, n):
+        raise ValueError("%s must be an int32 [%d, %d] matrix, got %s %s" % (name, P, n, t.dtype, tuple(t.shape)))
+    if n > 1 and t.stride(1) != 1:
+        raise ValueError("%s needs unit column stride" % name)
+    return t.data_ptr(), (t.stride(0) if P > 1 else n)
+
+
+def bar(w_f, w_r, out, iters, *, idx_f=None, idx_r=None, delta0=0.0, max_iterations=1000, rtol=1e-5):
+    """nfk_bar: out.shape[0] independent BAR solves in one launch.  w_f [n_f] and
+    w_r [n_r] fp32; idx_f [P, n_f] / idx_r [P, n_r] int32 row gathers (or both
+    None); out [P, 3] fp64 (DeltaF, lme_f, lme_r), iters [P] int32.  Index values
+    are the caller's responsibility: they are not validated."""
+    dev = _require_hip(w_f, w_r, out, iters, idx_f, idx_r)
+    if w_f.dim() != 1 or w_r.dim() != 1:
+        raise ValueError("w_f and w_r must be vectors, got %s and %s" % (tuple(w_f.shape), tuple(w_r.shape)))
+    n_f, n_r = w_f.numel(), w_r.numel()
+    if out.dim() != 2 or out.shape[1] != 3 or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float64 [P, 3] matrix")
+    P = out.shape[0]
+    fp, ldf = _idx_rows(idx_f, P, n_f, "idx_f")
+    rp, ldr = _idx_rows(idx_r, P, n_r, "idx_r")
+    _timed("nfk_bar", dev, "nfk_bar", _vec(w_f, n_f, "w_f"), n_f, _vec(w_r, n_r, "w_r"), n_r, fp, ldf, rp, ldr,
+           P, float(delta0), int(max_iterations), float(rtol), out.data_ptr(),
+           _vec(iters, P, "iters", torch.int32), _stream(dev))
+
+
 def trig_features(x, feat, B):
     dev = _require_hip(x, feat)
     n_rows, n = x.shape

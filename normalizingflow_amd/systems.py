@@ -17,8 +17,8 @@ what the Normal prior gets: the kernel with ``+ sign * log|det|`` fused, a
 status word for the reference's NaN ``ValueError``, an autograd node under
 training and HIP-graph capture (models._prior_log_prob).
 
-Out of scope: LAMMPS, Fe, the MBAR/BAR solvers and plotting.  HMC is in
-hmc.py.
+Out of scope: LAMMPS, Fe, MBAR and plotting.  HMC is in hmc.py, the BAR
+estimator in bar.py.
 """
 from __future__ import annotations
 

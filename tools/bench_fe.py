@@ -1,0 +1,205 @@
+#!/usr/bin/env python
+"""Times of the free-energy estimator (nfk_bar.hip, normalizingflow_amd/bar.py)
+on one GPU against the two host forms it replaces.
+
+    python tools/bench_fe.py [--out profiles/fe/bench_fe.json]
+
+Three forms of the same work alternate inside one process, window by window:
+
+  kernel  ``bar.bar_solve`` / ``bar.bootstrap`` / ``app.fe_estimates`` on fp32
+          device tensors: every problem of a call in one nfk_bar launch
+  torch   the same calls with ``bar.use_kernels = False``: the fp64 torch
+          iteration on the same GPU, one host sync per iteration
+  numpy   the work values (or Q) copied to the host, then an fp64 NumPy loop of
+          the same iteration; the copy is inside the timed call
+
+Shapes: one solve at n_f = n_r = 500, 2^16 and 2^20; a 200-replica bootstrap at
+500 and 2^16; ``fe_estimates`` from a device Q of 2^16 rows.  Work values are
+Crooks-consistent Gaussians (dF 37.5, s 2).  Every timed call ends in a device
+synchronise and is timed by the host clock (the host forms have no other
+clock); the kernel's device-event time is recorded next to it.  Warm-up
+precedes the timed windows; median, min and max over --windows windows.  Not
+the bench.py contract line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def numpy_bar(w_f, w_r, delta=0.0, max_iter=1000, rtol=1e-5):
+    """The iteration of normalizingflow_amd/bar.py in NumPy fp64: (DeltaF, iterations)."""
+    import numpy as np
+    n_f, n_r = w_f.size, w_r.size
+    M = math.log(n_f / n_r)
+
+    def g(a):
+        return -(np.maximum(a, 0.0) + np.log1p(np.exp(-np.abs(a))))
+
+    def lse(t):
+        m = t.max()
+        return math.log(np.exp(t - m).sum()) + m
+
+    for k in range(max_iter):
+        new = (lse(g((M - w_r) - delta) - w_r) - math.log(n_r)) - (lse(g((M + w_f) - delta)) - math.log(n_f))
+        stop = new != new or (k > 0 and abs((new - delta) / new) < rtol)
+        delta = new
+        if stop:
+            break
+    return delta, k + 1
+
+
+def timed(variants, nwin, budget_s):
+    """{name: fn} -> {name: {median_ms, min_ms, max_ms, calls}}: the variants
+    alternate inside every window; a window holds as many calls of a variant as
+    fit ``budget_s`` (at least one), fixed after the warm-up."""
+    import torch
+    calls = {}
+    for k, fn in variants.items():
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        calls[k] = max(1, min(50, int(budget_s / max(time.perf_counter() - t0, 1e-6))))
+    ms = {k: [] for k in variants}
+    for _ in range(nwin):
+        for k, fn in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls[k]):
+                fn()
+                torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3 / calls[k])
+    return {k: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4),
+                "max_ms": round(max(v), 4), "calls": calls[k]} for k, v in ms.items()}
+
+
+def device_ms(fn, reps=5):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return round(statistics.median(out), 4)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--budget", type=float, default=0.2, help="seconds of calls per variant and window")
+    ap.add_argument("--nboot", type=int, default=200)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "fe", "bench_fe.json"))
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from normalizingflow_amd import app
+    from normalizingflow_amd import bar as B
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/bench_fe.py needs a HIP device")
+    dev = torch.device("cuda", 0)
+
+    def torch_path(fn):
+        def run():
+            B.use_kernels = False
+            try:
+                return fn()
+            finally:
+                B.use_kernels = True
+        return run
+
+    def work(n, seed):
+        g = torch.Generator().manual_seed(seed)
+        w_f = 37.5 + 2.0 + 2.0 * torch.randn(n, generator=g)
+        w_r = -37.5 + 2.0 + 2.0 * torch.randn(n, generator=g)
+        return w_f.to(dev), w_r.to(dev)
+
+    res = {"tool": "tools/bench_fe.py", "device": torch.cuda.get_device_name(0), "windows": a.windows,
+           "budget_s": a.budget, "stage_cap": None, "solve": {}, "bootstrap": {}, "fe_estimates": {}}
+    from normalizingflow_amd import kernels as K_
+    res["stage_cap"] = K_.bar_stage_cap()
+
+    for n in (500, 1 << 16, 1 << 20):
+        w_f, w_r = work(n, n)
+        out, iters = B.bar_solve(w_f, w_r)
+        ref, ref_iters = numpy_bar(w_f.cpu().double().numpy(), w_r.cpu().double().numpy())
+        t_out, t_iters = torch_path(lambda: B.bar_solve(w_f, w_r))()
+        r = timed({"kernel": lambda: B.bar_solve(w_f, w_r),
+                   "torch": torch_path(lambda: B.bar_solve(w_f, w_r)),
+                   "numpy": lambda: numpy_bar(w_f.cpu().double().numpy(), w_r.cpu().double().numpy())},
+                  a.windows, a.budget)
+        r["kernel_device_ms"] = device_ms(lambda: B.bar_solve(w_f, w_r))
+        r["iterations"] = {"kernel": int(iters[0]), "torch": int(t_iters[0]), "numpy": ref_iters}
+        r["kernel_minus_numpy"] = float(out[0, 0]) - ref
+        r["torch_minus_numpy"] = float(t_out[0, 0]) - ref
+        res["solve"]["n%d" % n] = r
+        print("solve", n, json.dumps(r), flush=True)
+
+    for n in (500, 1 << 16):
+        w_f, w_r = work(n, n + 1)
+
+        def host_boot():
+            f, r_ = w_f.cpu().double().numpy(), w_r.cpu().double().numpy()
+            rng = np.random.default_rng(0)
+            return [numpy_bar(f[rng.integers(n, size=n)], r_[rng.integers(n, size=n)])[0] for _ in range(a.nboot)]
+
+        gen = torch.Generator(dev).manual_seed(0)
+        r = timed({"kernel": lambda: B.bootstrap(w_f, w_r, a.nboot, generator=gen),
+                   "torch": torch_path(lambda: B.bootstrap(w_f, w_r, a.nboot, generator=gen)),
+                   "numpy": host_boot}, a.windows, a.budget)
+        r["kernel_device_ms"] = device_ms(lambda: B.bootstrap(w_f, w_r, a.nboot, generator=gen))
+        r["nboot"] = a.nboot
+        r["form"] = "staged" if 2 * n <= res["stage_cap"] else "streamed"
+        res["bootstrap"]["n%d" % n] = r
+        print("bootstrap", n, json.dumps(r), flush=True)
+
+    n = 1 << 16
+    w_f, w_r = work(n, 7)
+    g = torch.Generator().manual_seed(8)
+    q00 = (-150.0 + 5.0 * torch.randn(n, generator=g)).to(dev)
+    q11 = (-180.0 + 5.0 * torch.randn(n, generator=g)).to(dev)
+    Q = torch.stack((torch.stack((q00, q00 - w_f), 1), torch.stack((q11 - w_r, q11), 1))).contiguous()
+    cfg = app.get_cfg_defaults()
+    cfg.dataset.nparticles, cfg.dataset.kT = 32, 2.0
+
+    def host_fe():
+        q = Q.cpu().numpy()
+        s0, s1 = q[1][:, 0].min(), q[1][:, 1].min()
+        q = q - np.array([s0, s1], dtype=q.dtype)
+        f, r_ = (q[0][:, 0] - q[0][:, 1]).astype(np.float64), (-q[1][:, 0] + q[1][:, 1]).astype(np.float64)
+        off = float(s0 - s1)
+        lme = [math.log(np.exp(w - w.max()).mean()) + w.max() for w in (f, r_)]
+        return tuple((off + v) / 32 * 2.0 for v in (numpy_bar(f, r_)[0], -lme[1], lme[0]))
+
+    ours = [float(v) for v in app.fe_estimates(cfg, Q)]
+    host = host_fe()
+    r = timed({"kernel": lambda: app.fe_estimates(cfg, Q), "torch": torch_path(lambda: app.fe_estimates(cfg, Q)),
+               "numpy": host_fe}, a.windows, a.budget)
+    r["kernel_device_ms"] = device_ms(lambda: app.fe_estimates(cfg, Q))
+    r["kernel_minus_numpy"] = [o - h for o, h in zip(ours, host)]
+    res["fe_estimates"]["rows%d" % n] = r
+    print("fe_estimates", n, json.dumps(r), flush=True)
+
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
