@@ -695,6 +695,71 @@ int nfk_hmc_accept(float* x_cur, int64_t ldc, const float* x_new, int64_t ldn, f
                    int32_t* naccept, int64_t chains, int32_t width, double beta, nfk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Whole HMC runs, nfk_hmc_run.hip: `epochs` moves of `chains` independent
+ * chains (nf/hmc.py:50-63) in ONE launch.  The random numbers are read, not
+ * made: v_draws [epochs, chains, W] dense holds the velocity draws, already
+ * scaled by sqrt(var), and r [epochs, chains] the uniforms.  Per chain c, with
+ * x = x_cur[c, :W] (row stride ldx) and u = u_cur[c] in registers, epoch e is
+ *   pos_rec[e, c, :] = x, pot_rec[e, c] = u      (both given or both null:
+ *                                                 entry e is the state BEFORE move e)
+ *   (x', v', u') = the system's nfk_*_trajectory from (x, v_draws[e, c, :]):
+ *                  path_len steps of the text above, the same device functions
+ *                  (step_x / step_v of nfk_step.h, the forces and the closing
+ *                  potential of nfk_systems_dev.h), the same group-sum tree, no
+ *                  contraction -- bit for bit that launch's x_out, v_out, pot_out
+ *   d = u - u';  hamiltonian: d = (d + k) - k'
+ *   accept iff r[e, c] < expf(d * (float)beta)    (nfk_hmc_accept's test; a NaN rejects)
+ *   accepted: x = x', u = u', count += 1
+ * and afterwards x_cur[c, :] = x, u_cur[c] = u, naccept[c] += count (int32,
+ * nullable) and v_last[c, :W] (row stride ldv, nullable) = the v' of the LAST
+ * epoch, accepted or not.  So without `hamiltonian` a run equals, bit for bit,
+ * `epochs` pairs of nfk_*_trajectory and nfk_hmc_accept launches fed the same
+ * draws.  With `hamiltonian` the kinetic energies are computed here, k from
+ * the draw and k' from v': each lane sums v*v over its own elements in
+ * ascending order, the lanes of the chain are summed by the group-sum
+ * butterfly, and the sum is multiplied by 0.5f.  This is the one place where
+ * the bits may differ from the per-epoch chain of launches, whose K is a torch
+ * row reduction in another order.
+ * Mapping (the trajectory kernels', with the chain's state on chip across the
+ * epochs): Einstein -- a chain on next_pow2(D) <= 64 lanes, up to 8 coordinates
+ * per lane (D = natoms*dim <= 512); mixture -- a particle per lane, up to 4 per
+ * lane (npart <= 256, nfk_gmix_supported); Lennard-Jones -- nfk_lj_trajectory's
+ * mapping (nfk_lj_supported), x in registers, the row staged in two LDS
+ * buffers, restaged from x after every decision whatever it was, so that every
+ * barrier sits in block-uniform control flow; rows past `chains` walk the
+ * barriers without touching memory.  The chain's first lane decides and
+ * broadcasts the decision.  Plain vector stores, no atomics, nothing between
+ * workgroups.  x_cur, v_last and the records do not overlap each other or the
+ * draws.
+ * The *_hmc_supported queries are host-only.  NFK_EINVAL, nothing launched:
+ * chains, epochs or path_len below zero; scheme outside {0, 1}; an unsupported
+ * shape; exactly one of pos_rec / pot_rec; and, with chains > 0 and
+ * epochs > 0, a null x_cur / u_cur / v_draws / r (or system parameter), ldx
+ * below W, or ldv below W with v_last given.  chains == 0 or epochs == 0
+ * returns 0 without a launch.
+ * ------------------------------------------------------------------------- */
+int nfk_einstein_hmc_supported(int32_t natoms, int32_t dim);
+int nfk_gmix_hmc_supported(int32_t npart, int32_t dim, int32_t ncenters);
+int nfk_lj_hmc_supported(int32_t n, int32_t dim);
+int nfk_einstein_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, const float* v_draws,
+                         const float* r, float* v_last, int64_t ldv, float* pos_rec, float* pot_rec,
+                         int64_t chains, int32_t epochs, int32_t path_len, double dt, double dt_sq,
+                         int32_t scheme, double beta, int32_t hamiltonian, const float* centers,
+                         int32_t natoms, int32_t dim, float scale, float half_log_det, int32_t has_box,
+                         double boxlength, nfk_stream_t stream);
+int nfk_gmix_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, const float* v_draws,
+                     const float* r, float* v_last, int64_t ldv, float* pos_rec, float* pot_rec,
+                     int64_t chains, int32_t epochs, int32_t path_len, double dt, double dt_sq,
+                     int32_t scheme, double beta, int32_t hamiltonian, const float* centers,
+                     const float* scales, const float* hlds, int32_t npart, int32_t dim, int32_t ncenters,
+                     nfk_stream_t stream);
+int nfk_lj_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, const float* v_draws,
+                   const float* r, float* v_last, int64_t ldv, float* pos_rec, float* pot_rec,
+                   int64_t chains, int32_t epochs, int32_t path_len, double dt, double dt_sq, int32_t scheme,
+                   double beta, int32_t hamiltonian, int32_t n, int32_t dim, double boxlength, double sigma,
+                   double epsilon, int32_t has_cutoff, double cutoff, int32_t shift, nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Bennett acceptance ratio (applications/src/bar.py:16-68), `problems`
  * independent solves in one launch, and the exponential averages of
  * test.py:67-68.  Problem p works on wf_i = w_f[idx_f ? idx_f[p*ldif + i] : i],

@@ -209,6 +209,26 @@ SIGNATURES = {
         P, I64, P, I64, P, P,           # x_cur, ldc, x_new, ldn, u_cur, u_new
         P, P, P, P,                     # k_cur, k_new, r, naccept
         I64, I32, F64, P]),             # chains, width, beta, stream
+    "nfk_einstein_hmc_supported": (ctypes.c_int, [I32, I32]),
+    "nfk_gmix_hmc_supported": (ctypes.c_int, [I32, I32, I32]),
+    "nfk_lj_hmc_supported": (ctypes.c_int, [I32, I32]),
+    "nfk_einstein_hmc_run": (ctypes.c_int, [
+        P, I64, P, P, P, P, P, I64, P, P,   # x_cur, ldx, u_cur, naccept, v_draws, r, v_last, ldv, pos_rec, pot_rec
+        I64, I32, I32, F64, F64, I32,   # chains, epochs, path_len, dt, dt_sq, scheme
+        F64, I32,                       # beta, hamiltonian
+        P, I32, I32, F32, F32,          # centers, natoms, dim, scale, half_log_det
+        I32, F64, P]),                  # has_box, boxlength, stream
+    "nfk_gmix_hmc_run": (ctypes.c_int, [
+        P, I64, P, P, P, P, P, I64, P, P,   # x_cur, ldx, u_cur, naccept, v_draws, r, v_last, ldv, pos_rec, pot_rec
+        I64, I32, I32, F64, F64, I32,   # chains, epochs, path_len, dt, dt_sq, scheme
+        F64, I32,                       # beta, hamiltonian
+        P, P, P, I32, I32, I32, P]),    # centers, scales, hlds, npart, dim, ncenters, stream
+    "nfk_lj_hmc_run": (ctypes.c_int, [
+        P, I64, P, P, P, P, P, I64, P, P,   # x_cur, ldx, u_cur, naccept, v_draws, r, v_last, ldv, pos_rec, pot_rec
+        I64, I32, I32, F64, F64, I32,   # chains, epochs, path_len, dt, dt_sq, scheme
+        F64, I32,                       # beta, hamiltonian
+        I32, I32,                       # n, dim
+        F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
     "nfk_bar_stage_cap": (ctypes.c_int, []),
     "nfk_bar": (ctypes.c_int, [
         P, I64, P, I64,                 # w_f, n_f, w_r, n_r

@@ -298,12 +298,16 @@ def _sim_positions(simulation, rows, dim):
     return rows
 
 
-def collect_hmc_data(cfg, model, hmc, burnin=100, epochs=500):
+def collect_hmc_data(cfg, model, hmc, burnin=100, epochs=500, one_launch=False):
     """dynamics.py:59-65 without the file writes: one model sample relaxed by
-    ``epochs`` HMC moves; returns (traj[burnin:], acceptance rate)."""
+    ``epochs`` HMC moves; returns (traj[burnin:], acceptance rate).
+    ``one_launch=True`` runs the epochs in one launch (``HMC.hmc``)."""
     samples, _, _ = model.sample(1)
     init = _sim_positions(hmc.simulation, samples.detach().reshape(1, -1), hmc.dim)[0]
-    traj, _, _, acc_prob = hmc.hmc(epochs=epochs, init_pos=init)
+    if one_launch:
+        traj, _, _, acc_prob = hmc.hmc(epochs=epochs, init_pos=init, one_launch=True)
+    else:
+        traj, _, _, acc_prob = hmc.hmc(epochs=epochs, init_pos=init)
     return traj[burnin:], acc_prob
 
 

@@ -12,25 +12,10 @@
 #include <cstdio>
 
 #include "../../include/nfk.h"
+#include "nfk_step.h"  // Step, step_x, step_v, make_step: shared with nfk_hmc_run.hip
 #include "nfk_systems_dev.h"
 
 namespace {
-
-// The integrator's constants: (float)dt, (float)dt_sq and the scheme.
-struct Step {
-    float dt, dt_sq;
-    int path_len, verlet;
-};
-
-// x' = (x + v dt) + (G 0.5) dt_sq
-__device__ __forceinline__ float step_x(float x, float v, float G, const Step& s) {
-    return (x + v * s.dt) + (G * 0.5f) * s.dt_sq;
-}
-
-// v' = v + (dt (G + Gn)) 0.5
-__device__ __forceinline__ float step_v(float v, float G, float Gn, const Step& s) {
-    return v + (s.dt * (G + Gn)) * 0.5f;
-}
 
 // ---------------------------------------------------------------------------
 // Einstein crystal: a coordinate's force depends on that coordinate alone, so a
@@ -263,17 +248,6 @@ int check_traj(const char* who, const void* x_in, int64_t ldxi, const void* v_in
     if (why == nullptr) return 0;
     std::snprintf(buf, sizeof(buf), "%s: %s", who, why);
     return nfk_set_error(buf);
-}
-
-inline Step make_step(int32_t path_len, double dt, double dt_sq, int32_t scheme) {
-    // dt and dt**2 are the reference's Python scalars: rounded to fp32 once, where
-    // the tensor op casts them
-    Step s;
-    s.dt = (float)dt;
-    s.dt_sq = (float)dt_sq;
-    s.path_len = path_len;
-    s.verlet = scheme;
-    return s;
 }
 
 }  // namespace

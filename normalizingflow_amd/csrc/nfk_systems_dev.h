@@ -1,7 +1,8 @@
 // nfk_systems_dev.h -- the device arithmetic of the applications layer's
 // systems (Einstein crystal, Gaussian mixture, Lennard-Jones) and the launch
 // helpers around it, shared by nfk_systems.hip (log-density / energy and their
-// backward passes) and nfk_dynamics.hip (whole trajectories in one launch).
+// backward passes), nfk_dynamics.hip (whole trajectories in one launch) and
+// nfk_hmc_run.hip (whole HMC runs in one launch).
 // One definition of every expression, so a force inside a trajectory has the
 // bits of the backward kernel's.  Include after <hip/hip_runtime.h>, <cmath>,
 // <cstdio> and nfk.h.

@@ -9,7 +9,8 @@ One epoch is one ``randn``, one trajectory launch (systems ``integration_step``)
 one ``rand`` and one Metropolis launch (nfk_hmc_accept); nothing in the loop
 waits for the device and nothing is printed.  On the CPU, in fp64 or with the
 simulation's ``use_kernels`` or ``fused_dynamics`` switched off the same steps
-run as torch ops.
+run as torch ops.  ``hmc(..., one_launch=True)`` draws the random numbers of
+many epochs in bulk and runs all of them in ONE launch (nfk_hmc_run.hip).
 
 As in the reference the default test accepts on the potential alone,
 ``exp((U_old - U_new) * beta)`` (hmc.py:56), and the default integrator is the
@@ -29,7 +30,7 @@ import torch
 from torch.distributions import MultivariateNormal
 
 from . import kernels as K_
-from .systems import LJ
+from .systems import LJ, _SCHEMES
 
 __all__ = ["HMC"]
 
@@ -145,7 +146,7 @@ class HMC:
         u_cur.copy_(torch.where(acc, u_new, u_cur))
         naccept += acc.to(torch.int32)
 
-    def hmc(self, epochs=1, init_pos=None, record=True):
+    def hmc(self, epochs=1, init_pos=None, record=True, one_launch=False, draw_bytes=1 << 28):
         """``epochs`` moves of every chain.  Returns the reference's 4-tuple:
         positions [epochs, C, W] and potentials [epochs, C] (entry i is the
         state BEFORE move i, hmc.py:53-54; one chain: [epochs, W] and
@@ -153,7 +154,29 @@ class HMC:
         (the mean over chains; the call's one host synchronisation).
         ``record=False`` stores nothing per epoch and returns the final
         positions and potentials in the first two slots.  ``self.naccept``
-        holds the per-chain counts."""
+        holds the per-chain counts.
+
+        ``one_launch=True`` draws the random numbers of many epochs at once
+        and runs those epochs in ONE launch (nfk_hmc_run.hip) instead of a
+        trajectory and a Metropolis launch per epoch.  The run is cut into
+        segments of ``e = max(1, min(remaining, draw_bytes // (4 * C * (W + 1))))``
+        epochs; a segment draws, in this order,
+
+            v = torch.randn(e, C, W, device=..., dtype=...) * sd    # sd = self._var(...).sqrt()
+            r = torch.rand(e, C, device=..., dtype=...)
+
+        and epoch i of the segment uses ``v[i]`` and ``r[i]``.  The result
+        depends on the seed and on ``draw_bytes`` alone, never on the route:
+        where the simulation does not take the kernel (CPU, fp64, a shape
+        beyond its limits, ``use_kernels`` or ``fused_dynamics`` off) the
+        segment runs as the per-epoch steps fed the same draws, and without
+        ``hamiltonian`` the two routes agree bit for bit (with it, the kernel
+        sums the kinetic energies in its own order, include/nfk.h).  The draw
+        order differs from the default path's (v, r, v, r, ...) unless a
+        segment is one epoch long.  ``one_launch=False`` is the per-epoch path,
+        unchanged."""
+        if one_launch:
+            return self._hmc_segments(epochs, init_pos, record, draw_bytes)
         sim = self.simulation
         if init_pos is not None:
             sim.set_position(init_pos)
@@ -184,6 +207,69 @@ class HMC:
                          u_new.reshape(chains), k_cur, k_new, r, naccept)
         sim.set_position(x_cur.view(shape))
         log_prob = None if v is None else self.log_prob(v)  # the reference returns the last draw's
+        self.naccept = naccept
+        self.position = x_cur.flatten() if single else x_cur
+        self.potential = u_cur
+        rate = float(naccept.double().mean()) / epochs if epochs else 0.0
+        if not record:
+            return self.position, (u_cur[0] if single else u_cur), log_prob, rate
+        if single:
+            return positions[:, 0], potentials[:, 0], log_prob, rate
+        return positions, potentials, log_prob, rate
+
+    def _hmc_segments(self, epochs, init_pos, record, draw_bytes):
+        """``hmc(one_launch=True)``: bulk draws and one launch per segment."""
+        sim = self.simulation
+        if self.scheme not in _SCHEMES:
+            raise ValueError("scheme must be 'reference' or 'verlet', got %r" % (self.scheme,))
+        if init_pos is not None:
+            sim.set_position(init_pos)
+        device, dtype, chains, single = self._like()
+        shape = sim.get_position().shape
+        W = self.width
+        with torch.no_grad():
+            x_cur = sim.get_position().detach().reshape(chains, W).clone()
+            u_cur = sim.get_potential().detach().reshape(chains).clone()
+        naccept = torch.zeros(chains, dtype=torch.int32, device=device)
+        positions = potentials = None
+        if record:
+            positions = torch.empty(epochs, chains, W, dtype=dtype, device=device)
+            potentials = torch.empty(epochs, chains, dtype=u_cur.dtype, device=device)
+        sd = self._var(device, dtype).sqrt()
+        run = getattr(sim, "_hmc_run", None)
+        v = v_last = None
+        done = 0
+        while done < epochs:
+            e = max(1, min(epochs - done, int(draw_bytes) // (4 * max(1, chains) * (W + 1))))
+            v = torch.randn(e, chains, W, device=device, dtype=dtype) * sd
+            r = torch.rand(e, chains, device=device, dtype=u_cur.dtype)
+            pos = positions[done:done + e] if record else None
+            pot = potentials[done:done + e] if record else None
+            v_out = None if run is None else torch.empty_like(x_cur)
+            if run is not None and run(x_cur, u_cur, naccept, v, r, shape=shape, path_len=self.path_len,
+                                       dt=self.dt, sch=_SCHEMES[self.scheme], beta=self.beta,
+                                       hamiltonian=self.hamiltonian, v_last=v_out, pos_rec=pos, pot_rec=pot):
+                v_last = v_out.view(shape)
+            else:
+                for i in range(e):
+                    if record:
+                        pos[i].copy_(x_cur)
+                        pot[i].copy_(u_cur)
+                    sim.set_position(x_cur.view(shape))
+                    sim.set_velocity(v[i].flatten() if single else v[i])
+                    x_new, u_new = sim.integration_step(self.path_len, self.dt, scheme=self.scheme)
+                    k_cur = k_new = None
+                    if self.hamiltonian:
+                        k_cur, k_new = self._kinetic(v[i], chains), self._kinetic(sim.get_velocity(), chains)
+                    x_new = x_new.reshape(chains, W)
+                    self._accept(x_cur, x_new if x_new.stride(-1) == 1 else x_new.contiguous(), u_cur,
+                                 u_new.reshape(chains), k_cur, k_new, r[i], naccept)
+                v_last = sim.get_velocity()
+            done += e
+        sim.set_position(x_cur.view(shape))
+        if v_last is not None:
+            sim.set_velocity(v_last)
+        log_prob = None if v is None else self.log_prob(v[-1])  # the reference returns the last draw's
         self.naccept = naccept
         self.position = x_cur.flatten() if single else x_cur
         self.potential = u_cur

@@ -622,6 +622,84 @@ def hmc_accept(x_cur, x_new, u_cur, u_new, r, naccept, *, beta, k_cur=None, k_ne
            _vec(naccept, C, "naccept", torch.int32), C, W, float(beta), _stream(dev))
 
 
+# whole HMC runs in one launch (nfk_hmc_run.hip)
+def einstein_hmc_supported(natoms, dim):
+    return bool(_lib.load().nfk_einstein_hmc_supported(natoms, dim))
+
+
+def gmix_hmc_supported(npart, dim, ncenters):
+    return bool(_lib.load().nfk_gmix_hmc_supported(npart, dim, ncenters))
+
+
+def lj_hmc_supported(n, dim):
+    return bool(_lib.load().nfk_lj_hmc_supported(n, dim))
+
+
+def _hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, width, path_len, dt, scheme,
+                  beta, hamiltonian):
+    if x_cur.dim() != 2 or x_cur.shape[1] != width:
+        raise ValueError("x_cur must be [C, %d], got %s" % (width, tuple(x_cur.shape)))
+    C = x_cur.shape[0]
+    if v_draws.dim() != 3 or v_draws.shape[1:] != (C, width):
+        raise ValueError("v_draws must be [E, %d, %d], got %s" % (C, width, tuple(v_draws.shape)))
+    E = v_draws.shape[0]
+    xp, ldx = _mat(x_cur, "x_cur")
+    vp, ldv = (None, 0)
+    if v_last is not None:
+        if v_last.shape != x_cur.shape:
+            raise ValueError("v_last must be %s, got %s" % (tuple(x_cur.shape), tuple(v_last.shape)))
+        vp, ldv = _mat(v_last, "v_last")
+    if (pos_rec is None) != (pot_rec is None):
+        raise ValueError("pos_rec and pot_rec come together")
+    if scheme not in (0, 1):
+        raise ValueError("scheme must be 0 (the reference's lagged force) or 1 (velocity Verlet)")
+    dt = float(dt)
+    return (xp, ldx, _vec(u_cur, C, "u_cur"), _vec(naccept, C, "naccept", torch.int32),
+            _vec(v_draws, E * C * width, "v_draws"), _vec(r, E * C, "r"), vp, ldv,
+            _vec(pos_rec, E * C * width, "pos_rec"), _vec(pot_rec, E * C, "pot_rec"), C, E, int(path_len), dt,
+            dt ** 2, int(scheme), float(beta), 1 if hamiltonian else 0)
+
+
+def einstein_hmc_run(x_cur, u_cur, naccept, v_draws, r, centers, *, path_len, dt, scheme, beta, scale, hld,
+                     boxlength=None, hamiltonian=False, v_last=None, pos_rec=None, pot_rec=None):
+    """nfk_einstein_hmc_run: all ``v_draws.shape[0]`` epochs of every row of
+    ``x_cur`` [C, W] in one launch, in place in x_cur, u_cur and naccept.
+    ``v_draws`` [E, C, W] and ``r`` [E, C] are the draws; ``pos_rec`` [E, C, W]
+    and ``pot_rec`` [E, C] (both or neither) take the state before each move,
+    ``v_last`` [C, W] the last trajectory's final velocity."""
+    dev = _require_hip(x_cur, u_cur, naccept, v_draws, r, centers, v_last, pos_rec, pot_rec)
+    natoms, dim = centers.shape
+    has_box, L = _box(boxlength)
+    _timed("nfk_einstein_hmc_run", dev, "nfk_einstein_hmc_run",
+           *_hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, natoms * dim, path_len,
+                          dt, scheme, beta, hamiltonian),
+           _vec(centers, natoms * dim, "centers"), natoms, dim, float(scale), float(hld), has_box, L,
+           _stream(dev))
+
+
+def gmix_hmc_run(x_cur, u_cur, naccept, v_draws, r, centers, scales, hlds, *, path_len, dt, scheme, beta,
+                 npart, hamiltonian=False, v_last=None, pos_rec=None, pot_rec=None):
+    """nfk_gmix_hmc_run; arguments as ``einstein_hmc_run``."""
+    dev = _require_hip(x_cur, u_cur, naccept, v_draws, r, centers, scales, hlds, v_last, pos_rec, pot_rec)
+    M, dim = centers.shape
+    _timed("nfk_gmix_hmc_run", dev, "nfk_gmix_hmc_run",
+           *_hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, int(npart) * dim,
+                          path_len, dt, scheme, beta, hamiltonian),
+           _vec(centers, M * dim, "centers"), _vec(scales, M, "scales"), _vec(hlds, M, "hlds"), int(npart),
+           dim, M, _stream(dev))
+
+
+def lj_hmc_run(x_cur, u_cur, naccept, v_draws, r, *, path_len, dt, scheme, beta, n, dim, boxlength, sigma=1.0,
+               epsilon=1.0, cutoff=None, shift=True, hamiltonian=False, v_last=None, pos_rec=None,
+               pot_rec=None):
+    """nfk_lj_hmc_run; rows are [n*dim], other arguments as ``einstein_hmc_run``."""
+    dev = _require_hip(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec)
+    _timed("nfk_lj_hmc_run", dev, "nfk_lj_hmc_run",
+           *_hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, n * dim, path_len, dt,
+                          scheme, beta, hamiltonian),
+           n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
+
+
 def bar_stage_cap():
     """Largest n_f + n_r whose work values nfk_bar keeps in LDS."""
     return int(_lib.load().nfk_bar_stage_cap())

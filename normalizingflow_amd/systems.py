@@ -207,6 +207,25 @@ class _Dynamics:
         with torch.no_grad():
             return x, v, self.potential(x)
 
+    def _hmc_run(self, x_cur, u_cur, naccept, v, r, *, shape, path_len, dt, sch, beta, hamiltonian,
+                 v_last=None, pos_rec=None, pot_rec=None):
+        """All ``v.shape[0]`` HMC epochs of the chains x_cur [C, W] in ONE launch
+        (nfk_hmc_run.hip), in place in x_cur, u_cur and naccept; ``v`` [E, C, W]
+        and ``r`` [E, C] are the draws and ``shape`` is the shape the simulation
+        holds the chains' positions in.  Returns False, having done nothing,
+        when the tensors or the shape do not take the kernel (CPU, fp64,
+        ``use_kernels`` or ``fused_dynamics`` off, shape not supported): the
+        caller then runs the per-epoch steps."""
+        f32 = torch.float32
+        if not (self.fused_dynamics and x_cur.is_cuda and all(
+                torch.is_tensor(t) and t.dtype == f32 and t.device == x_cur.device for t in (x_cur, u_cur, v, r))
+                and self._hmc_ok(x_cur, shape)):
+            return False
+        self._hmc_launch(shape, x_cur, u_cur, naccept, v, r, path_len=int(path_len),
+                         dt=0.005 if dt is None else dt, scheme=sch, beta=beta, hamiltonian=hamiltonian,
+                         v_last=v_last, pos_rec=pos_rec, pot_rec=pot_rec)
+        return True
+
     def integration_step(self, path_len=1, dt=0.005, init_pos=None, init_velocity=None, scheme="reference"):
         """``path_len`` steps of ``dt`` (None: 0.005) from the held position and
         velocity (or ``init_pos`` / ``init_velocity``); returns (position,
@@ -351,6 +370,13 @@ class EinsteinCrystal(_KernelBacked):
         K_.einstein_trajectory(x, v, xo, vo, pot, self.centers, path_len=path_len, dt=dt, scheme=sch,
                                scale=scale, hld=hld, boxlength=self.boxlength)
 
+    def _hmc_ok(self, x_cur, shape):
+        return self._kernel_ok(x_cur) and K_.einstein_hmc_supported(self.natoms, self.dim)
+
+    def _hmc_launch(self, shape, *args, **kw):
+        scale, hld = self._consts()
+        K_.einstein_hmc_run(*args, self.centers, scale=scale, hld=hld, boxlength=self.boxlength, **kw)
+
     def _log_prob_torch(self, x):
         if self._validate_args:
             _raise_nan(x, self)
@@ -475,6 +501,13 @@ class GaussianMixture(_KernelBacked):
         scales, hlds = self._consts()
         K_.gmix_trajectory(x, v, xo, vo, pot, self.centers, scales, hlds, path_len=path_len, dt=dt,
                            scheme=sch, npart=self.nparticles)
+
+    def _hmc_ok(self, x_cur, shape):
+        return self._kernel_ok(x_cur) and K_.gmix_hmc_supported(self.nparticles, self.dim, self.ncenters)
+
+    def _hmc_launch(self, shape, *args, **kw):
+        scales, hlds = self._consts()
+        K_.gmix_hmc_run(*args, self.centers, scales, hlds, npart=self.nparticles, **kw)
 
     def sample(self, nsamples, flatten=True):
         with torch.no_grad():
@@ -620,6 +653,14 @@ class LJ(_Dynamics):
     def _trajectory(self, x, v, xo, vo, pot, path_len, dt, sch):
         n, dim = self._traj_nd  # the rows are [n*dim]: _integrate notes the split
         K_.lj_trajectory(x, v, xo, vo, pot, path_len=path_len, dt=dt, scheme=sch, n=n, dim=dim, **self._kw())
+
+    def _hmc_ok(self, x_cur, shape):
+        # no box: the per-epoch steps raise the reference's TypeError
+        return (self.use_kernels and self.boxlength is not None and len(shape) >= 2
+                and K_.lj_hmc_supported(shape[-2], shape[-1]))
+
+    def _hmc_launch(self, shape, *args, **kw):
+        K_.lj_hmc_run(*args, n=shape[-2], dim=shape[-1], **self._kw(), **kw)
 
     def _integrate(self, x, v, path_len, dt, sch, keep_force=False):
         if x.dim() < 2:

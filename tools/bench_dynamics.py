@@ -16,6 +16,16 @@ rows, path_len 12 (the two launches of ``relaxation_step`` on 500 frames with
 npoints 10), and one HMC epoch (path_len 12) at 1 and 500 chains.  Warm-up
 precedes the timed windows; times are device-event windows (median, min, max
 over --windows windows of --iters calls).  Not the bench.py contract line.
+
+    python tools/bench_dynamics.py --hmc-run [--out profiles/dynamics/bench_hmc_run.json]
+
+times a whole ``hmc(500)`` (path_len 12, records kept, as ``collect_hmc_data``
+calls it) for one chain and 500 chains of the same two systems, again two forms
+alternating window by window:
+
+  one_launch  ``hmc(500, one_launch=True)``: bulk draws and ONE nfk_*_hmc_run launch
+  per_epoch   the default ``hmc(500)``: a trajectory and a Metropolis launch per
+              epoch -- the code as it was before the one-launch kernels, the yardstick
 """
 from __future__ import annotations
 
@@ -39,7 +49,7 @@ def fcc32():
     return (torch.tensor(pts, dtype=torch.float64) * L32 - L32 / 2 + L32 / 8).float()
 
 
-def windows(variants, iters, nwin):
+def windows(variants, iters, nwin, ratio=("fused", "per_step")):
     """{name: fn} -> {name: {median_ms, min_ms, max_ms}} per call; the variants
     alternate inside every window round."""
     import torch
@@ -59,7 +69,7 @@ def windows(variants, iters, nwin):
             ms[k].append(e0.elapsed_time(e1) / iters)
     out = {k: {"median_ms": round(statistics.median(v), 5), "min_ms": round(min(v), 5),
                "max_ms": round(max(v), 5)} for k, v in ms.items()}
-    out["fused_over_per_step"] = round(out["fused"]["median_ms"] / out["per_step"]["median_ms"], 4)
+    out["%s_over_%s" % ratio] = round(out[ratio[0]]["median_ms"] / out[ratio[1]]["median_ms"], 4)
     return out
 
 
@@ -87,16 +97,57 @@ def start(kind, rows, dev):
     return x.to(dev), torch.randn(rows, 96, generator=g).to(dev), 0.005
 
 
+def hmc_run_rows(a, dev):
+    """hmc(--epochs) in both forms; the two are first checked against each other on
+    a short run: same seed, one epoch per launch so that the draws coincide,
+    bit-equal records."""
+    import torch
+    from normalizingflow_amd.hmc import HMC
+    res = {"tool": "tools/bench_dynamics.py --hmc-run", "device": torch.cuda.get_device_name(0),
+           "iters": a.iters, "windows": a.windows, "path_len": a.path_len, "epochs": a.epochs, "hmc_run": {}}
+    for kind in ("lj", "einstein"):
+        sim, _ = systems_pair(kind, dev)
+        for chains in (1, 500):
+            x, _, dt = start(kind, chains, dev)
+            run = HMC(sim, path_len=a.path_len, dt=dt)
+            torch.manual_seed(0)
+            pa = run.hmc(8, x, one_launch=True, draw_bytes=0)[0]  # one epoch per launch: the default's draw order
+            torch.manual_seed(0)
+            pb = run.hmc(8, x)[0]
+            assert torch.equal(pa, pb), "the two forms differ"
+            r = windows({"one_launch": lambda: run.hmc(a.epochs, x, one_launch=True),
+                         "per_epoch": lambda: run.hmc(a.epochs, x)}, a.iters, a.windows,
+                        ratio=("one_launch", "per_epoch"))
+            r["note"] = "one hmc(%d) call with records: start potential, draws, epochs, closing synchronisation" % a.epochs
+            res["hmc_run"]["%s_chains%d" % (kind, chains)] = r
+            print(kind, "hmc(%d)" % a.epochs, chains, json.dumps(r), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=None, help="calls per window (10; --hmc-run: 3)")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--path-len", type=int, default=12)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "dynamics", "bench_dynamics.json"))
+    ap.add_argument("--hmc-run", action="store_true", help="time hmc(--epochs) in one launch against per epoch")
+    ap.add_argument("--epochs", type=int, default=500)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.iters is None:
+        a.iters = 3 if a.hmc_run else 10
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "dynamics",
+                             "bench_hmc_run.json" if a.hmc_run else "bench_dynamics.json")
     import torch
     from normalizingflow_amd.hmc import HMC
     dev = torch.device("cuda", 0)
+    if a.hmc_run:
+        res = hmc_run_rows(a, dev)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res))
+        return 0
     res = {"tool": "tools/bench_dynamics.py", "device": torch.cuda.get_device_name(0), "iters": a.iters,
            "windows": a.windows, "path_len": a.path_len, "trajectory": {}, "hmc_epoch": {}}
     for kind in ("lj", "einstein"):
