@@ -467,6 +467,7 @@ FusedArgs fused_args(const float* x, int64_t ldx, const float* wpack, const int3
     {
         // NSF_CL's spline constants (flows.py:236-237 defaults), evaluated like the
         // reference's Python scalars (nfk_make_const), folded for the fixed-point knots
+        // (wide kernel) and as plain floats for knot_phase's float knots
         const NfkSplineConst sc =
             nfk_make_const(K, -tail_bound, tail_bound, -tail_bound, tail_bound, 1, 1e-3, 1e-3, 1e-3);
         const float two30 = 1073741824.0f;
@@ -476,6 +477,10 @@ FusedArgs fused_args(const float* x, int64_t ldx, const float* wpack, const int3
         a.c.inv30 = two30 / sc.span;
         a.c.fb30 = sc.fw * two30;
         a.c.mb30 = sc.min_w * two30;
+        a.c.span = sc.span;
+        a.c.inv_span = 1.0f / sc.span;
+        a.c.fb = sc.fw;
+        a.c.min_bin = sc.min_w;
         a.c.m2b = sc.m2b;
         a.c.min_d = sc.min_d;
         a.c.d_edge = sc.d_edge;

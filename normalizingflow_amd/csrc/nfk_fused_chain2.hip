@@ -378,12 +378,8 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                     h1[s][t] = f32x4{bv.x * bsc, bv.y * bsc, bv.z * bsc, bv.w * bsc};
                 }
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float v = e[j] * sx;
-                    const _Float16 hh = (_Float16)v;
-                    xh[s][j] = hh;
-                    xl8[s][j] = (_Float16)(v - (float)hh);
-                }
+                for (int j = 0; j < 8; ++j) e[j] *= sx;
+                split8(e, xh[s], xl8[s]);
             }
 #pragma unroll
             for (int t = 0; t < HT; ++t) {

@@ -13,6 +13,7 @@
 int nfk_set_error(const char* msg);  // nfk_kernels.hip
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 namespace nfk_fused {
 
@@ -175,6 +176,12 @@ struct FusedConst {
     float sp30;       // 2B * 2^-30: fixed-point prefix -> edge offset
     float inv30;      // 2^30 / 2B: x -> fixed-point domain
     float fb30, mb30; // (1 - min_bin K) 2^30, min_bin 2^30: floored fractions in fixed point
+                      // (sp30 .. mb30: the wide kernel, nfk_fused_wide.h; knot_phase uses
+                      // the float constants below)
+    float span;       // 2B: normalised knot -> edge offset
+    float inv_span;   // 1 / 2B: x -> the normalised knot range [0, 1]
+    float fb;         // 1 - min_bin K: the softmax's share of the floored fractions
+    float min_bin;    // floor of a bin's fraction (width and height alike)
     float m2b;        // 2B log2(e): second softmax (nfk_knots_nsf_lean)
     float min_d;      // min_derivative
     float d_edge;     // min_d + softplus(pad constant): boundary derivative
@@ -395,6 +402,17 @@ __device__ __forceinline__ uint32_t f16_residual_pair(float v0, float v1, uint32
     return r;
 }
 
+// fp16 split (hi, lo) of 8 values (layer 1's scaled inputs)
+__device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) hi[j] = (_Float16)v[j];
+    const u32x4 hp = __builtin_bit_cast(u32x4, hi);
+    u32x4 lp;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) lp[p] = f16_residual_pair(v[2 * p], v[2 * p + 1], hp[p]);
+    lo = __builtin_bit_cast(h8, lp);
+}
+
 // B fragments (hi, lo) of k-block kb from the activations of tiles 2kb, 2kb+1
 template <int HT>
 __device__ __forceinline__ void split_act(const f32x4 (&a)[HT], int kb, h8& hi, h8& lo) {
@@ -562,31 +580,39 @@ __device__ __forceinline__ void act_operands(f32x4 (&h)[HT], float c2, h8 (&bh)[
 #pragma unroll
     for (int kb = 0; kb < KBH; ++kb) split_act<HT>(h, kb, bh[kb], bl[kb]);
     if constexpr (T1) {
-        h4 hi, lo;
+        h4 hi;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float v = tanh_scaled(h[HT - 1][r], c2);
             h[HT - 1][r] = v;  // (kept like the other tiles' activations: store_act reads them)
             hi[r] = (_Float16)v;
-            lo[r] = (_Float16)(v - (float)hi[r]);
         }
-        btail = ((threadIdx.x >> 4) & 3) == 1 ? lo : hi;
+        const u32x2 hp = __builtin_bit_cast(u32x2, hi);
+        u32x2 lp;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) lp[p] = f16_residual_pair(h[HT - 1][2 * p], h[HT - 1][2 * p + 1], hp[p]);
+        btail = ((threadIdx.x >> 4) & 3) == 1 ? __builtin_bit_cast(h4, lp) : hi;
     } else {
         btail = h4{0, 0, 0, 0};
     }
 }
 
 // Knot phase epilogue: for the 4 coordinates of this lane, turn the K logits
-// of register r into fixed-point knot prefixes (NSF_CL's 2B softmax, then
-// RQS's softmax, floor and cumsum: nfk_prefix_nsf_lean; the logits still carry
+// of register r into knots of the normalised range [0, 1] (NSF_CL's 2B softmax,
+// then RQS's softmax, floor and cumsum: the float partial sums of
+// nfk_partials_nsf_lean, one fma per interior knot; the logits still carry
 // the 2^(s3+14) product scale, which l2e absorbs) and keep (edge_k, size_k) of
-// the bin.  The searched phase finds the bin in the integer domain:
-// floor((x - lo) 2^30 / 2B) >= pre[j] counts the interior edges <= x, which is
+// the bin.  The searched phase finds the bin in the normalised domain:
+// (x - lo) / 2B >= t[j] counts the interior edges <= x, which is
 // the bin of utils.py:20-25 for every x inside the tails (edges are strictly
-// increasing; elements within an ulp of an edge may take the neighbouring
+// increasing: consecutive knots differ by at least min_bin;
+// elements within an ulp of an edge may take the neighbouring
 // bin, where the C1 spline agrees); the other phase selects by k.
-// The two prefixes at the bin are read back from a per-wave LDS table (row j =
-// prefix j of every lane, one ds_read2st64 at row k).  Tried: 2 (K-1) selects on
+// Until round 8 the knots were 2^-30 fixed-point integer prefixes (still so in
+// the wide kernel): 14 converts and integer adds per softmax more, no more
+// accurate (tools/knot_forms.py).
+// The two knots at the bin are read back from a per-wave LDS table (row j =
+// knot j of every lane, one ds_read2st64 at row k).  Tried: 2 (K-1) selects on
 // compare masks, c3 6.69 vs 6.28 ms per chain, and an
 // unsigned-minimum search without the table (section 10).
 // Tried: the knot prefixes of coordinate pairs in packed fp32 -- 7 % fewer VALU
@@ -610,30 +636,30 @@ __device__ __forceinline__ void knot_phase(const f32x4 (&acc)[K], const float (&
 #endif
 #pragma unroll
     for (int r = R0; r < R1; ++r) {
-        float u[K];
-        int pre[K];
+        float u[K], t[K];
 #pragma unroll
-        for (int t = 0; t < K; ++t) u[t] = acc[t][r];
-        // the second softmax's sum: NaN iff a logit was NaN
-        const float s2 = nfk_prefix_nsf_lean<K>(u, l2e, c.m2b, c.fb30, c.mb30, pre);
-        // the knot range's left end, NaN iff the logits were: the reference's NaN
-        // cumsum makes every edge NaN (the integer prefixes would drop it)
-        const float lo = __builtin_fmaf(s2, 0.0f, c.lo);
+        for (int i = 0; i < K; ++i) u[i] = acc[i][r];
+        // t[j]: knot j of the normalised range [0, 1] (t[0] = 0); a NaN logit
+        // makes every t[j], j >= 1, NaN like the reference's NaN cumsum
+        const float s2 = nfk_partials_nsf_lean<K>(u, l2e, c.m2b, t);
+        const float f = c.fb * __builtin_amdgcn_rcpf(s2);
+#pragma unroll
+        for (int j = 1; j < K; ++j) t[j] = __builtin_fmaf(t[j], f, (float)j * c.min_bin);
         if (SEARCH) {
-            const int xi = __float2int_rd(__builtin_fmaf(xv[r], c.inv30, -c.lo * c.inv30));
+            const float xn = __builtin_fmaf(xv[r], c.inv_span, -c.lo * c.inv_span);
             int k = 0;
 #pragma unroll
-            for (int j = 1; j < K; ++j) k += (xi >= pre[j]) ? 1 : 0;
+            for (int j = 1; j < K; ++j) k += (xn >= t[j]) ? 1 : 0;
             kb[r] = k;
         }
         const int kk = kb[r];
-        // rows 0..K-1; p1 is unused when kk = K - 1 (e1 = hi below)
+        // rows 0..K-1 (float bits); t1 is unused when kk = K - 1 (e1 = hi below)
 #pragma unroll
-        for (int j = 0; j < K; ++j) scr[j * 64 + lane] = pre[j];
-        const int p0 = scr[kk * 64 + lane];
-        const int p1 = scr[(kk + 1 < K ? kk + 1 : K - 1) * 64 + lane];
-        const float e = __builtin_fmaf(c.sp30, (float)p0, lo);
-        float e1 = __builtin_fmaf(c.sp30, (float)p1, lo);
+        for (int j = 0; j < K; ++j) scr[j * 64 + lane] = __builtin_bit_cast(int, t[j]);
+        const float t0 = __builtin_bit_cast(float, scr[kk * 64 + lane]);
+        const float t1 = __builtin_bit_cast(float, scr[(kk + 1 < K ? kk + 1 : K - 1) * 64 + lane]);
+        const float e = __builtin_fmaf(c.span, t0, c.lo);
+        float e1 = __builtin_fmaf(c.span, t1, c.lo);
         // computed for every lane, then selected: as a conditional the compiler
         // sank the LUT read into a branch with its own LDS wait
         asm volatile("" : "+v"(e1));
@@ -1042,12 +1068,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, SPLIT ? kNsfWpeSplit : kNsfWpe) voi
                 if (kb > 0) x_operand(kb, u, v);
                 const float xv8[8] = {u.x * sx, u.y * sx, u.z * sx, u.w * sx, v.x * sx, v.y * sx, v.z * sx, v.w * sx};
                 h8 xh, xl8;
-    #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const _Float16 hh = (_Float16)xv8[j];
-                    xh[j] = hh;
-                    xl8[j] = (_Float16)(xv8[j] - (float)hh);
-                }
+                split8(xv8, xh, xl8);
     #pragma unroll
                 for (int t = 0; t < HT; ++t) {
                     const h8 ahi = __builtin_bit_cast(h8, s[((kb * HT + t) * 2) * 64 + lane]);

@@ -211,6 +211,35 @@ __device__ __forceinline__ float nfk_prefix_nsf_lean(const float (&raw)[K], floa
     return s2;
 }
 
+// The same double softmax kept in float: E[j] = sum_{i<j} of the second
+// softmax's terms (E[0] = 0), the partial sums the sequential nfk_sum forms on
+// its way to s2 = E[K-1] + e[K-1], which is returned -- one chain of K - 1
+// adds gives the cumsum and the sum.  Knot j of the normalised range [0, 1] is
+// fma(E[j], fb / s2, j min_bin); no integer conversion.  A NaN logit makes
+// every E[j], j >= 1, and s2 NaN, so the knots carry it themselves.
+// Knot error against fp64 (tools/knot_forms.py): no larger than the fixed-point
+// form's; the exps dominate it, not the cumsum.
+template <int K>
+__device__ __forceinline__ float nfk_partials_nsf_lean(const float (&raw)[K], float l2e, float m2b,
+                                                       float (&E)[K]) {
+    const float m = nfk_max_lean<K>(raw);
+    const float mL = m * l2e;
+    float e[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(raw[i], l2e, -mL));
+    const float q = m2b * __builtin_amdgcn_rcpf(nfk_sum<K>(e));
+#pragma unroll
+    for (int i = 0; i < K; ++i) e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], q, -m2b));
+    E[0] = 0.0f;
+    float s = e[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i) {
+        E[i] = s;
+        s = s + e[i];
+    }
+    return s;
+}
+
 // nfk_prefix_nsf_lean for two coordinates at once: the fp32 FMAs, multiplies
 // and sums run as packed pairs (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32,
 // two lanes' worth of work per VALU instruction); max, exp2, rcp and the
