@@ -457,8 +457,9 @@ extern "C" int nfk_planar_bwd(const float* x, int64_t ldx, const float* w, const
                               float* gw, float* gu, float* gb, void* workspace, int64_t batch, int32_t dim,
                               int32_t nonlinearity, nfk_stream_t stream) {
     if (batch < 0 || dim <= 0 || dim > 16384) return nfk_set_error("nfk_planar_bwd: bad sizes");
-    if (!x || !w || !u || !b || !gx || !gw || !gu || !gb || !workspace)
-        return nfk_set_error("nfk_planar_bwd: null pointer");
+    if (!w || !u || !b || !gw || !gu || !gb || !workspace) return nfk_set_error("nfk_planar_bwd: null pointer");
+    // an empty batch has null row tensors: the parameter gradients are zero
+    if (batch > 0 && (!x || !gx)) return nfk_set_error("nfk_planar_bwd: null pointer");
     if (nonlinearity < 0 || nonlinearity > 2) return nfk_set_error("nfk_planar_bwd: bad nonlinearity");
     hipStream_t st = (hipStream_t)stream;
     Ws ws = ws_carve(workspace, batch, dim);

@@ -120,7 +120,7 @@ extern "C" int nfk_actnorm(const float* x, int64_t ldx, const float* mu, const f
     if (batch < 0 || dim <= 0) return nfk_set_error("nfk_actnorm: bad sizes");
     if (!mu || !log_sigma) return nfk_set_error("nfk_actnorm: null pointer");
     if (batch > 0 && (!x || !z)) return nfk_set_error("nfk_actnorm: null pointer");
-    if (logdet_mode != 0 && !logdet) return nfk_set_error("nfk_actnorm: null logdet");
+    if (batch > 0 && logdet_mode != 0 && !logdet) return nfk_set_error("nfk_actnorm: null logdet");
     hipLaunchKernelGGL(k_actnorm, dim3(grid_for(batch * (int64_t)dim, 256)), dim3(256), 0,
                        (hipStream_t)stream, x, ldx, mu, log_sigma, dim, z, ldz, logdet,
                        logdet_mode, ld_scalar, batch, inverse);
