@@ -800,6 +800,45 @@ int nfk_bar(const float* w_f, int64_t n_f, const float* w_r, int64_t n_r, const 
             int64_t ldif, const int32_t* idx_r, int64_t ldir, int64_t problems, double delta0,
             int32_t max_iterations, double rtol, double* out, int32_t* iters, nfk_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Multistate free energies (the MBAR equations behind `emus`, test.py:61-63,
+ * and the driver of test.py:74-88), `problems` independent solves in one
+ * launch.  u [rows, K] holds fp32 reduced energies, sample-major with row
+ * stride ldu; problem p works on the N rows idx ? idx[p*ldi + n] : n (int32 row
+ * gathers, e.g. stratified bootstrap resamples).  n_k (HOST int64[K], each >= 1,
+ * summing to N) are the states' sample counts and f0 (HOST double[K], or null
+ * for zeros) the start; both are read during the call and passed to the kernel
+ * by value (the counts also as log n_k).  Inputs are promoted once; all
+ * arithmetic is fp64 without contraction, in the gauge f_0 = 0.
+ * One iteration at f: pass A accumulates, with a_k = (log n_k + f_k) - u_nk and
+ * W_k = exp(a_k - max a) / sum_k exp(a_k - max a) in [0, 1], S_k = sum_n W_nk
+ * and G_jk = sum_n W_nj W_nk; one lane forms f_sc = f - log(S / n), re-gauged,
+ * and f_nr = f - H_r^{-1} g_r with g = S - n, H = diag(S) - G on states
+ * 1..K-1 (Cholesky; a pivot not > 0 or a non-finite entry makes it invalid);
+ * pass B evaluates |S - n|^2 at both, and f' = f_nr iff it is valid and its
+ * norm is strictly smaller (a NaN falls to f_sc).  The loop stops when
+ * max_i |f'_i - f_i| < rtol * max_i |f'_i| (from the first iteration on), at
+ * max_iterations, or at once on a NaN iterate, which is returned; rtol = 0
+ * returns exactly the max_iterations-th iterate.  f[p*K + k] = the last f',
+ * iters[p] = iterations done, gram[p*K*K + j*K + k] = G_jk at the returned f
+ * (the full symmetric matrix, from one more pass A).  Every loop exit compares
+ * one LDS word read by all lanes: the trip count is workgroup-uniform and
+ * bounded by max_iterations.
+ * One workgroup per problem (256, 512 or 1024 threads by N * K alone, K >= 6
+ * at most 512; grid-stride above 4096 problems), no atomics.  N * K <=
+ * nfk_mbar_stage_cap(): the energies are gathered once into LDS, state-major;
+ * otherwise every pass re-reads them through the index row.  Fixed-order
+ * reductions: two runs are bitwise equal.  Index values are not validated.
+ * NFK_EINVAL, nothing launched: !nfk_mbar_supported(K) (2 <= K <= 8), an
+ * n_k < 1, sum n_k != N, problems < 1, max_iterations < 1, rtol < 0 or NaN,
+ * ldu < K, ldi < N, null u / n_k / f / iters / gram, problems > 1 without idx.
+ * ------------------------------------------------------------------------- */
+int nfk_mbar_supported(int32_t K); /* host-only */
+int nfk_mbar_stage_cap(void);      /* host-only: largest N * K kept in LDS */
+int nfk_mbar(const float* u, int64_t ldu, int64_t N, int32_t K, const int64_t* n_k, const int32_t* idx,
+             int64_t ldi, int64_t problems, const double* f0, int32_t max_iterations, double rtol,
+             double* f, int32_t* iters, double* gram, nfk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

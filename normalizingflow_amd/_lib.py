@@ -235,6 +235,13 @@ SIGNATURES = {
         P, I64, P, I64,                 # idx_f, ldif, idx_r, ldir
         I64, F64, I32, F64,             # problems, delta0, max_iterations, rtol
         P, P, P]),                      # out, iters, stream
+    "nfk_mbar_supported": (ctypes.c_int, [I32]),
+    "nfk_mbar_stage_cap": (ctypes.c_int, []),
+    "nfk_mbar": (ctypes.c_int, [
+        P, I64, I64, I32, P,            # u, ldu, N, K, n_k (host int64[K])
+        P, I64, I64, P,                 # idx, ldi, problems, f0 (host double[K] or null)
+        I32, F64,                       # max_iterations, rtol
+        P, P, P, P]),                   # f, iters, gram, stream
 }
 
 _lock = threading.Lock()

@@ -18,7 +18,10 @@ restated for the flow path.
   ``q_matrix_relaxed`` -- the same through ``relaxation_step``.
 * ``fe_estimates`` / ``fe_diff`` -- the free-energy estimates of test.py:55-68
   (BAR and the two exponential averages) over bar.py's batched solver, with
-  bootstrap errors; Q never leaves its device.
+  bootstrap errors, and on request the multistate ``emus`` of test.py:61-63
+  with its asymptotic error (mbar.py); Q never leaves its device.
+* ``fe_diff_no_training`` -- the prior-against-target driver of test.py:74-88
+  over mbar.py's solver.
 * ``collect_hmc_data`` / ``integrate_out_v`` / ``relaxation_step`` -- the
   dynamics of applications/src/dynamics.py over systems.py's own integrators
   (no LAMMPS), every trajectory of a call in one launch.
@@ -36,6 +39,7 @@ import yaml
 
 from . import bar as bar_
 from . import flows as F_
+from . import mbar as mbar_
 from . import systems
 from .hmc import HMC
 from .models import NormalizingFlowModel
@@ -43,7 +47,8 @@ from .models import NormalizingFlowModel
 __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flows", "build_prior",
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
            "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
-           "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff"]
+           "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff",
+           "fe_diff_no_training"]
 
 
 class CfgNode(dict):
@@ -358,7 +363,7 @@ def q_matrix_relaxed(cfg, model, potential, nsamples, batchsize=500, **relaxatio
     return torch.stack((Q0, Q1)).detach()
 
 
-def fe_estimates(cfg, Q, nboot=0, generator=None):
+def fe_estimates(cfg, Q, nboot=0, generator=None, emus=False):
     """test.py:55-68 from a [2, N, 2] Q on any device: the offsets
     ``to_subtract_0/1`` (the minima of Q[1]'s columns), the work values
     ``w_F = Q[0,:,0] - Q[0,:,1]`` and ``w_R = -Q[1,:,0] + Q[1,:,1]`` of the
@@ -371,8 +376,20 @@ def fe_estimates(cfg, Q, nboot=0, generator=None):
     as 0-d fp64 tensors on Q's device; nothing synchronises.  With ``nboot`` > 0
     the bootstrap standard deviations ``(bar_err, md_err, nf_err)`` follow
     (``nboot`` resamples of w_F and w_R, ``bar.bootstrap``).  Q is not modified
-    (the reference shifts it in place).  ``emus`` (test.py:61-63) and the MBAR
-    error (test.py:70) are not restated: their solver is a private package."""
+    (the reference shifts it in place).
+
+    ``emus=True`` appends the multistate estimate of test.py:61-63 to the
+    estimates, ``(bar, md, nf, emus)`` as test.py:72 returns them:
+
+        emus = (off + f_1 - f_0) / nparticles * kT   (f: mbar.mbar_solve(-Q))
+
+    with ``log c_0 - log c_1 = f_1 - f_0`` for the normalising constants
+    ``c = exp(-f)`` of ``MBAR(-Q).norm_const()``, from one solve on the shifted
+    Q run to convergence (the reference caps its plain iteration at 40).  With
+    ``nboot`` > 0 as well the errors follow as ``(bar_err, md_err, nf_err,
+    emus_err)``; ``emus_err`` is the asymptotic standard deviation of f_1 - f_0
+    from the same solve's Gram matrix (``mbar.mbar_std``), scaled like emus, in
+    place of the private solver's error of test.py:70."""
     d = cfg.dataset
     Q = Q.detach()
     if Q.dim() != 3 or Q.shape[0] != 2 or Q.shape[2] != 2:
@@ -388,24 +405,57 @@ def fe_estimates(cfg, Q, nboot=0, generator=None):
 
     out, _ = bar_.bar_solve(w_F, w_R)
     est = scaled(out[0])
+    if emus:
+        n_k = [Q.shape[1]] * 2
+        f, _, gram = mbar_.mbar_solve((-Qs).reshape(-1, 2), n_k)
+        est = est + ((off + (f[0, 1] - f[0, 0])) / d.nparticles * d.kT,)
     if not nboot:
         return est
     boot = scaled(bar_.bootstrap(w_F, w_R, nboot, generator=generator))
-    return est + tuple(b.std() for b in boot)
+    err = tuple(b.std() for b in boot)
+    if emus:
+        err = err + (mbar_.mbar_std(gram, n_k, 0, 1)[0] / d.nparticles * d.kT,)
+    return est + err
 
 
 def fe_diff(cfg, model, potential, nsamples, relaxation=False, return_err=False, nboot=200, batchsize=500,
-            *, generator=None, relaxation_kw=None):
+            *, generator=None, relaxation_kw=None, emus=False):
     """test.py:33-72: ``(bar, md, nf)`` free-energy differences per particle
     between the flow and its target from ``nsamples`` samples of each
     (``relaxation=True``: both relaxed by ``relaxation_step`` first, called with
     ``relaxation_kw``).  ``return_err=True`` appends the bootstrap standard
     deviations ``(bar_err, md_err, nf_err)`` over ``nboot`` resamples.  Every
     result is a 0-d fp64 tensor on the model's device.  No file is written and
-    nothing is plotted; ``emus`` and the MBAR error of test.py:61-63, 70 are not
-    restated (see ``fe_estimates``)."""
+    nothing is plotted.  ``emus=True`` appends the multistate estimate of
+    test.py:61-63 to the estimates and, with ``return_err=True``, its asymptotic
+    standard deviation to the errors (see ``fe_estimates``)."""
     if relaxation:
         Q = q_matrix_relaxed(cfg, model, potential, nsamples, batchsize=batchsize, **(relaxation_kw or {}))
     else:
         Q = q_matrix(cfg, model, potential, nsamples, batchsize=batchsize)
-    return fe_estimates(cfg, Q, nboot=nboot if return_err else 0, generator=generator)
+    return fe_estimates(cfg, Q, nboot=nboot if return_err else 0, generator=generator, emus=emus)
+
+
+def fe_diff_no_training(cfg, model, potential, nsamples):
+    """test.py:74-88: the free energies of the model's prior (state 0) and the
+    target (state 1) from ``nsamples`` samples of each, without the flow:
+    ``kT * f / nparticles`` as a [2] fp64 tensor on the prior's device, f from
+    ``mbar.mbar_solve`` in the gauge f_0 = 0 (the reference prints FastMBAR's
+    ``F``).  Two deliberate differences from the reference's text: it scores
+    ``traj0`` twice (line 79 evaluates the prior on the prior's own samples
+    again, where the target's samples ``traj1`` are meant), and it divides by a
+    literal 54; here the prior scores ``traj1`` and the divisor is
+    ``cfg.dataset.nparticles``.  Nothing is plotted or printed."""
+    d = cfg.dataset
+    traj0 = model.prior.sample((nsamples,))
+    q00 = model.prior.log_prob(traj0)
+    q01 = -(potential.potential(traj0.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(q00.device)
+    traj1 = potential.sample(nsamples)
+    traj1 = traj1.reshape(len(traj1), -1).to(q00.device)
+    q10 = model.prior.log_prob(traj1)
+    q11 = -(potential.potential(traj1.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(q00.device)
+    Q0 = torch.transpose(torch.vstack((q00, q01)), 0, 1)
+    Q1 = torch.transpose(torch.vstack((q10, q11)), 0, 1)
+    u = -torch.cat((Q0, Q1), dim=0).detach()
+    f, _, _ = mbar_.mbar_solve(u, [len(traj0), len(traj1)])
+    return d.kT * f[0] / d.nparticles

@@ -23,8 +23,8 @@ Both paths differ from the reference's text in two ways: ``g`` is evaluated as
 ``-(max(a, 0) + log1p(exp(-|a|)))``, finite for every finite a (the reference's
 form shifts by min(a, 0) and overflows for |a| >~ 709), and a NaN iterate ends
 the loop at once and is returned (the reference spins to maximum_iterations
-and returns the same NaN).  The MBAR error estimate of test.py:70 is not
-restated; ``bootstrap`` stands in for it.
+and returns the same NaN).  ``bootstrap`` gives the errors of these estimates;
+the multistate estimate of test.py:61-63 and its asymptotic error are mbar.py's.
 """
 from __future__ import annotations
 

@@ -735,6 +735,49 @@ def bar(w_f, w_r, out, iters, *, idx_f=None, idx_r=None, delta0=0.0, max_iterati
            _vec(iters, P, "iters", torch.int32), _stream(dev))
 
 
+def mbar_supported(K):
+    """True for the state counts nfk_mbar is built for (2 <= K <= 8)."""
+    return bool(_lib.load().nfk_mbar_supported(int(K)))
+
+
+def mbar_stage_cap():
+    """Largest N * K whose reduced energies nfk_mbar keeps in LDS."""
+    return int(_lib.load().nfk_mbar_stage_cap())
+
+
+def mbar(u, n_k, f, iters, gram, *, idx=None, f0=None, max_iterations=1000, rtol=1e-8):
+    """nfk_mbar: f.shape[0] independent MBAR solves in one launch.  u [rows, K]
+    fp32 with unit column stride; n_k the K host counts (each >= 1, N = their
+    sum); idx [P, N] int32 row gathers (None: one problem on the N rows of u);
+    f0 K host floats or None; f [P, K] fp64, iters [P] int32, gram [P, K, K]
+    fp64.  Index values are the caller's responsibility: they are not validated."""
+    dev = _require_hip(u, f, iters, gram, idx)
+    up, ldu = _mat(u, "u")
+    K = u.shape[1]
+    counts = [int(n) for n in n_k]
+    if len(counts) != K:
+        raise ValueError("n_k holds %d counts but u has %d columns" % (len(counts), K))
+    if not mbar_supported(K):
+        raise ValueError("nfk_mbar is built for 2 <= K <= 8 states, got %d" % K)
+    if min(counts) < 1:
+        raise ValueError("every n_k must be at least 1, got %s" % (counts,))
+    N = sum(counts)
+    if f.dim() != 2 or f.shape[1] != K or f.dtype != torch.float64 or not f.is_contiguous():
+        raise ValueError("f must be a contiguous float64 [P, %d] matrix" % K)
+    P = f.shape[0]
+    if gram.shape != (P, K, K) or gram.dtype != torch.float64 or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous float64 [%d, %d, %d] tensor" % (P, K, K))
+    if idx is None and (P != 1 or u.shape[0] != N):
+        raise ValueError("without idx there is one problem on the sum n_k = %d rows of u (P %d, rows %d)"
+                         % (N, P, u.shape[0]))
+    ip, ldi = _idx_rows(idx, P, N, "idx")
+    if f0 is not None and len(f0) != K:
+        raise ValueError("f0 must hold K = %d values" % K)
+    _timed("nfk_mbar", dev, "nfk_mbar", up, ldu, N, K, (ctypes.c_int64 * K)(*counts), ip, ldi, P,
+           None if f0 is None else (ctypes.c_double * K)(*[float(v) for v in f0]), int(max_iterations),
+           float(rtol), f.data_ptr(), _vec(iters, P, "iters", torch.int32), gram.data_ptr(), _stream(dev))
+
+
 def trig_features(x, feat, B):
     dev = _require_hip(x, feat)
     n_rows, n = x.shape

@@ -3,6 +3,7 @@
 on one GPU against the two host forms it replaces.
 
     python tools/bench_fe.py [--out profiles/fe/bench_fe.json]
+    python tools/bench_fe.py --mbar [--out profiles/fe/bench_mbar.json]
 
 Three forms of the same work alternate inside one process, window by window:
 
@@ -20,6 +21,12 @@ synchronise and is timed by the host clock (the host forms have no other
 clock); the kernel's device-event time is recorded next to it.  Warm-up
 precedes the timed windows; median, min and max over --windows windows.  Not
 the bench.py contract line.
+
+``--mbar`` times the multistate solver (nfk_mbar.hip, normalizingflow_amd/
+mbar.py) instead, by the same method and in the same three forms: one solve and
+a 200-replica stratified bootstrap of 500 + 500 samples at K = 2 (the work
+values above as two states) and of 4,096 samples of K = 8 states (512 each,
+harmonic wells with offsets of 40 per state: N K is the kernel's LDS cap).
 """
 from __future__ import annotations
 
@@ -55,6 +62,40 @@ def numpy_bar(w_f, w_r, delta=0.0, max_iter=1000, rtol=1e-5):
         if stop:
             break
     return delta, k + 1
+
+
+def numpy_mbar(u, n_k, max_iter=1000, rtol=1e-8):
+    """The iteration of normalizingflow_amd/mbar.py in NumPy fp64: (f, iterations)."""
+    import numpy as np
+    n = np.asarray(n_k, dtype=np.float64)
+    logn = np.log(n)
+
+    def weights(f):
+        a = (logn + f)[None, :] - u
+        e = np.exp(a - a.max(axis=1, keepdims=True))
+        return e / e.sum(axis=1, keepdims=True)
+
+    f = np.zeros(len(n))
+    for k in range(max_iter):
+        W = weights(f)
+        S, G = W.sum(axis=0), W.T @ W
+        f_sc = f - np.log(S / n)
+        f_sc = f_sc - f_sc[0]
+        new, H = f_sc, (np.diag(S) - G)[1:, 1:]
+        try:
+            np.linalg.cholesky(H)
+            f_nr = np.concatenate((f[:1], f[1:] - np.linalg.solve(H, (S - n)[1:])))
+            if np.all(np.isfinite(f_nr)):
+                g_sc, g_nr = weights(f_sc).sum(axis=0) - n, weights(f_nr).sum(axis=0) - n
+                if np.dot(g_nr, g_nr) < np.dot(g_sc, g_sc):
+                    new = f_nr
+        except np.linalg.LinAlgError:
+            pass
+        stop = np.any(np.isnan(new)) or np.max(np.abs(new - f)) < rtol * np.max(np.abs(new))
+        f = new
+        if stop:
+            break
+    return f, k + 1
 
 
 def timed(variants, nwin, budget_s):
@@ -103,8 +144,11 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--budget", type=float, default=0.2, help="seconds of calls per variant and window")
     ap.add_argument("--nboot", type=int, default=200)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "fe", "bench_fe.json"))
+    ap.add_argument("--mbar", action="store_true", help="time the multistate solver instead")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "fe", "bench_mbar.json" if a.mbar else "bench_fe.json")
     import numpy as np
     import torch
     from normalizingflow_amd import app
@@ -128,9 +172,11 @@ def main():
         w_r = -37.5 + 2.0 + 2.0 * torch.randn(n, generator=g)
         return w_f.to(dev), w_r.to(dev)
 
+    from normalizingflow_amd import kernels as K_
+    if a.mbar:
+        return main_mbar(a, dev, work)
     res = {"tool": "tools/bench_fe.py", "device": torch.cuda.get_device_name(0), "windows": a.windows,
            "budget_s": a.budget, "stage_cap": None, "solve": {}, "bootstrap": {}, "fe_estimates": {}}
-    from normalizingflow_amd import kernels as K_
     res["stage_cap"] = K_.bar_stage_cap()
 
     for n in (500, 1 << 16, 1 << 20):
@@ -193,6 +239,76 @@ def main():
     r["kernel_minus_numpy"] = [o - h for o, h in zip(ours, host)]
     res["fe_estimates"]["rows%d" % n] = r
     print("fe_estimates", n, json.dumps(r), flush=True)
+
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+    return 0
+
+
+def main_mbar(a, dev, work):
+    import numpy as np
+    import torch
+    from normalizingflow_amd import kernels as K_
+    from normalizingflow_amd import mbar as M
+
+    def torch_path(fn):
+        def run():
+            M.use_kernels = False
+            try:
+                return fn()
+            finally:
+                M.use_kernels = True
+        return run
+
+    def two_states(n):
+        w_f, w_r = work(n, n)
+        u = torch.zeros(2 * n, 2, device=dev)
+        u[:n, 1] = w_f
+        u[n:, 0] = w_r
+        return u, [n, n]
+
+    def wells(K, n):
+        g = torch.Generator().manual_seed(K * n)
+        mu, sig = torch.linspace(0.0, 2.0, K), torch.linspace(1.0, 0.5, K)
+        x = (mu.repeat_interleave(n) + sig.repeat_interleave(n) * torch.randn(K * n, generator=g)).double()
+        u = 0.5 * ((x[:, None] - mu[None, :].double()) / sig[None, :].double()) ** 2 + 40.0 * torch.arange(K)
+        return u.float().to(dev), [n] * K
+
+    res = {"tool": "tools/bench_fe.py --mbar", "device": torch.cuda.get_device_name(0), "windows": a.windows,
+           "budget_s": a.budget, "stage_cap": K_.mbar_stage_cap(), "solve": {}, "bootstrap": {}}
+    for name, (u, n_k) in (("k2_n500", two_states(500)), ("k8_n4096", wells(8, 512))):
+        K, N = len(n_k), sum(n_k)
+        form = "staged" if N * K <= res["stage_cap"] else "streamed"
+        f, iters, _ = M.mbar_solve(u, n_k)
+        ref, ref_iters = numpy_mbar(u.cpu().double().numpy(), n_k)
+        t_f, t_iters, _ = torch_path(lambda: M.mbar_solve(u, n_k))()
+        r = timed({"kernel": lambda: M.mbar_solve(u, n_k), "torch": torch_path(lambda: M.mbar_solve(u, n_k)),
+                   "numpy": lambda: numpy_mbar(u.cpu().double().numpy(), n_k)}, a.windows, a.budget)
+        r["kernel_device_ms"] = device_ms(lambda: M.mbar_solve(u, n_k))
+        r["iterations"] = {"kernel": int(iters[0]), "torch": int(t_iters[0]), "numpy": ref_iters}
+        r["kernel_minus_numpy"] = float((f[0].cpu() - torch.from_numpy(ref)).abs().max())
+        r["torch_minus_numpy"] = float((t_f[0].cpu() - torch.from_numpy(ref)).abs().max())
+        r["K"], r["N"], r["form"] = K, N, form
+        res["solve"][name] = r
+        print("solve", name, json.dumps(r), flush=True)
+
+        def host_boot():
+            h = u.cpu().double().numpy()
+            rng = np.random.default_rng(0)
+            offs = np.concatenate(([0], np.cumsum(n_k)[:-1]))
+            return [numpy_mbar(h[np.concatenate([o + rng.integers(n, size=n) for o, n in zip(offs, n_k)])], n_k)[0]
+                    for _ in range(a.nboot)]
+
+        gen = torch.Generator(dev).manual_seed(0)
+        r = timed({"kernel": lambda: M.bootstrap(u, n_k, a.nboot, generator=gen),
+                   "torch": torch_path(lambda: M.bootstrap(u, n_k, a.nboot, generator=gen)),
+                   "numpy": host_boot}, a.windows, a.budget)
+        r["kernel_device_ms"] = device_ms(lambda: M.bootstrap(u, n_k, a.nboot, generator=gen))
+        r["nboot"], r["K"], r["N"], r["form"] = a.nboot, K, N, form
+        res["bootstrap"][name] = r
+        print("bootstrap", name, json.dumps(r), flush=True)
 
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
