@@ -626,6 +626,49 @@ int nfk_lj_potential_bwd(const float* x, int64_t ldx, const float* g, float* gx,
                          nfk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Embedded-atom energy from setfl tables, nfk_eam.hip (systems.py EAM): n atoms
+ * of one species in a periodic orthorhombic box (lx, ly, lz), x [batch, n*3]
+ * (row stride ldx) -> out [batch]:
+ *   rho_i = sum_(j,s) f(r_ijs)
+ *   U     = sum_i F(rho_i) + 1/2 sum_i sum_(j,s) z(r_ijs) / r_ijs
+ * s runs over integer image shifts, r_ijs = |x_i - x_j + s*L|, and a term counts
+ * when 0 < r_ijs <= rc: EVERY periodic image inside the cutoff, self images
+ * (i == j, s != 0) included; only r == 0 is skipped (the atom itself, and a
+ * coincident atom).  Each component of x_i - x_j is wrapped once into
+ * [-L/2, L/2], v - (float)L * rint(v * (float)(1/L)); then the shifts -n_a..n_a,
+ * n_a = floor(rc / L_a + 0.5) (at most 8), are visited per axis, x outermost,
+ * ascending, the component being v + (float)s * (float)L.  j is the outer loop.
+ * Tables: piecewise cubics, one quadruple (c3, c4, s, y) per interval m with
+ * value ((c3 p + c4) p + s) p + y at p = t - m, t = x * (float)(1 / dx), and
+ * derivative ((3 c3 p + 2 c4) p + s) * (float)(1 / dx).
+ *   rtab [2 (nr - 1)] float4: f's quadruple at [2m], z's (z = r phi) at [2m + 1];
+ *     m = min((int)t, nr - 2), p clamped to 1.
+ *   ftab [nrho - 1] float4: F's; m = (int)t clamped to [0, nrho - 2], p not
+ *     clamped below 0; from rho_max = (nrho - 1) drho on (and for a NaN)
+ *     F = f_end + fp_end (rho - rho_max), f_end and fp_end being F and dF/drho
+ *     at the last node.
+ * Both tables are device pointers, 16-byte aligned.
+ * Backward: gx[b, i] = g[b] * sum_(j != i, s) [phi' + (F'(rho_i) + F'(rho_j)) f'] d / r
+ * with phi = z / r and phi' = (z' - phi) / r: the exact gradient of the
+ * interpolated energy (self images do not depend on x_i).
+ * Layout as nfk_lj_potential (a row on next_pow2(n) <= 64 lanes, up to 4 atoms
+ * per lane, the row staged in LDS as float4); fixed-order sums, no atomics;
+ * the backward leaves F'(rho_j) beside x_j in LDS between its two (j, s) loops.
+ * Supported shapes: nfk_eam_supported() != 0 (n <= 256).  nr or nrho < 2, a
+ * spacing, box length or cutoff <= 0, rc / L_a > 8, misaligned tables:
+ * NFK_EINVAL, nothing launched.
+ * ------------------------------------------------------------------------- */
+int nfk_eam_supported(int32_t n);
+int nfk_eam_potential(const float* x, int64_t ldx, float* out, int64_t batch, int32_t n,
+                      const float* rtab, int32_t nr, double dr, const float* ftab, int32_t nrho,
+                      double drho, double f_end, double fp_end, double lx, double ly, double lz,
+                      double rc, nfk_stream_t stream);
+int nfk_eam_potential_bwd(const float* x, int64_t ldx, const float* g, float* gx, int64_t ldgx,
+                          int64_t batch, int32_t n, const float* rtab, int32_t nr, double dr,
+                          const float* ftab, int32_t nrho, double drho, double f_end, double fp_end,
+                          double lx, double ly, double lz, double rc, nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Dynamics of the three systems, nfk_dynamics.hip: integration_step
  * (systems.py:297-338, 382-401) for a batch of independent trajectories in ONE
  * launch, and the Metropolis step of HMC (nf/hmc.py:56-63).

@@ -191,6 +191,16 @@ SIGNATURES = {
         P, I64, P, P, I64,              # x, ldx, g, gx, ldgx
         I64, I32, I32,                  # batch, n, dim
         F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_eam_supported": (ctypes.c_int, [I32]),
+    "nfk_eam_potential": (ctypes.c_int, [
+        P, I64, P, I64, I32,            # x, ldx, out, batch, n
+        P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
+        F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
+    "nfk_eam_potential_bwd": (ctypes.c_int, [
+        P, I64, P, P, I64,              # x, ldx, g, gx, ldgx
+        I64, I32,                       # batch, n
+        P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
+        F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
     "nfk_einstein_trajectory": (ctypes.c_int, [
         P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
         I64, I32, F64, F64, I32,        # batch, path_len, dt, dt_sq, scheme

@@ -10,8 +10,9 @@ restated for the flow path.
   and NSF_CL mask cycle) and the priors of setup.py:17-30: "Normal",
   "EinsteinCrystal" and "GaussianMixture" (systems.py).
 * ``build_potential`` -- the target distribution of setup.py:76-80
-  (EinsteinCrystal, GaussianMixture, LJ); the LAMMPS-backed Fe and SimData
-  are out of scope.
+  (EinsteinCrystal, GaussianMixture, LJ, and Fe as ``systems.EAM`` when
+  ``dataset.eam_file`` names a setfl table); LAMMPS itself and SimData are
+  out of scope.
 * ``reverse_kl`` / ``forward_kl`` -- the losses of setup.py:90-100;
   ``q_matrix`` -- the Q matrix of test.py:33-50 (generate_from_nf, evaluate
   and the target's energies), up to ``Q = torch.stack(...)``;
@@ -106,7 +107,7 @@ def get_cfg_defaults():
                     nparticles=32, dim=3, kT=1.0, rho=None, ncellx=None, ncelly=None, ncellz=None,
                     cell_len=None, boxlength=None, periodic=True, type="xyz", sigma=1.0,
                     epsilon=1.0, cutoff=1.6, shift=True, centers=None, vars=None, alpha=None,
-                    input_dir=None)
+                    input_dir=None, eam_file=None)
     return _node(
         device="cuda:0",
         dataset=dataset,
@@ -174,9 +175,14 @@ def _parse_potential(name, c, device, what):
     if name == "LJ" and what == "potential":
         return systems.LJ(pos_dir=c.data, boxlength=c.boxlength, device=device, sigma=c.sigma,
                           epsilon=c.epsilon, cutoff=c.cutoff, shift=c.shift)
-    raise NotImplementedError("%s %r is not built here (systems.py holds EinsteinCrystal, GaussianMixture "
-                              "and LJ; LAMMPS-backed Fe and SimData are out of scope); pass an object "
-                              "instead" % (what, name))
+    if name == "Fe" and what == "potential" and c.eam_file is not None:
+        # the reference's LAMMPS input (input_dir) is not read: the setfl table is the model
+        box = tuple(nc * c.cell_len for nc in (c.ncellx, c.ncelly, c.ncellz))
+        return systems.EAM(c.eam_file, box, nparticles=c.nparticles, pos_dir=c.data, device=device)
+    raise NotImplementedError("%s %r is not built here (systems.py holds EinsteinCrystal, GaussianMixture, "
+                              "LJ and EAM; potential 'Fe' needs dataset.eam_file, a setfl table, and is no "
+                              "prior; LAMMPS itself and SimData are out of scope); pass an object instead"
+                              % (what, name))
 
 
 def build_prior(cfg, device):
@@ -190,9 +196,10 @@ def build_prior(cfg, device):
 def build_potential(cfg, mode="training", device=None):
     """The target of setup.py:76-80: ``cfg.dataset.data`` is set from
     training_data / testing_data by ``mode``, then ``cfg.dataset.potential``
-    (EinsteinCrystal, GaussianMixture, LJ or Normal) is built from
-    ``cfg.dataset``.  As in setup_model, a missing ``dataset.boxlength``
-    becomes 2 B first."""
+    (EinsteinCrystal, GaussianMixture, LJ, Normal, or Fe with
+    ``dataset.eam_file``: ``systems.EAM`` in the box ``(ncellx, ncelly,
+    ncellz) * cell_len``) is built from ``cfg.dataset``.  As in setup_model, a
+    missing ``dataset.boxlength`` becomes 2 B first."""
     device = cfg.device if device is None else device
     if cfg.dataset.boxlength is None and tail_bound(cfg) is not None:
         cfg.dataset.boxlength = 2 * tail_bound(cfg)
@@ -297,8 +304,8 @@ def q_matrix(cfg, model, potential, nsamples, batchsize=500):
 
 
 def _sim_positions(simulation, rows, dim):
-    """[B, W] rows in the shape the simulation holds positions in (LJ: [B, n, dim])."""
-    if isinstance(simulation, systems.LJ):
+    """[B, W] rows in the shape the simulation holds positions in (LJ, EAM: [B, n, dim])."""
+    if isinstance(simulation, (systems.LJ, systems.EAM)):
         return rows.reshape(rows.shape[0], -1, dim)
     return rows
 

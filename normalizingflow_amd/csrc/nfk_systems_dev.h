@@ -223,6 +223,129 @@ inline LjConst lj_const(double L, double sigma, double epsilon, int has_cutoff, 
     return k;
 }
 
+// ---------------------------------------------------------------------------
+// Embedded-atom model from setfl tables (systems.py EAM)
+// ---------------------------------------------------------------------------
+struct EamConst {
+    float lf[3], il[3];  // (float)L_a, (float)(1 / L_a)
+    int ns[3];           // n_a = floor(rc / L_a + 0.5): the image shifts are -n_a..n_a
+    int ks[3];           // how many consecutive shifts of one axis can be within rc of one atom
+    float rc, rcp, rc2p; // the cutoff; the cutoff and its square, padded (pre-filters only)
+    float inv_dr, inv_drho;
+    float rho_max, f_end, fp_end;  // (Nrho - 1) drho, F and dF/drho there
+    int nr2, nrho2;      // Nr - 2, Nrho - 2: the last interval of each table
+};
+
+// the cubic of one interval, q = (c3, c4, s, y): ((c3 p + c4) p + s) p + y, and its p-derivative
+__device__ __forceinline__ float eam_cubic(const float4 q, float p) { return ((q.x * p + q.y) * p + q.z) * p + q.w; }
+__device__ __forceinline__ float eam_dcubic(const float4 q, float p) {
+    return ((3.0f * q.x) * p + 2.0f * q.y) * p + q.z;
+}
+
+// F(rho) (DERIV: dF/drho): the table's cubic, below zero that of interval 0 continued,
+// from rho_max on the straight line through the last node with its slope.  A NaN takes
+// the line and touches no table entry.
+template <bool DERIV>
+__device__ __forceinline__ float eam_embed(float rho, const float4* __restrict__ ftab, const EamConst& k) {
+    if (!(rho < k.rho_max)) return DERIV ? k.fp_end : k.f_end + k.fp_end * (rho - k.rho_max);
+    const float t = rho * k.inv_drho;
+    const int m = max(0, min((int)t, k.nrho2));
+    const float p = t - (float)m;
+    const float4 q = ftab[m];
+    return DERIV ? eam_dcubic(q, p) * k.inv_drho : eam_cubic(q, p);
+}
+
+// Every image (i, j, s) of one pair.  The pair vector is wrapped once into
+// [-L/2, L/2] per component; the terms are visited in ascending (sx, sy, sz) and a
+// term counts when 0 < r <= rc.  Per axis only the shifts that can bring this
+// lane's component within the (padded) cutoff are walked, starting at the lane's
+// own lowest: a superset of the counted terms in the same order, so the sums have
+// the bits of the full -n_a..n_a scan.  rtab holds, per interval m, the quadruples
+// of f at [2m] and of z = r phi at [2m + 1].
+// MODE 0: rho += f, e += phi.  MODE 1: rho += f.  MODE 2: g += [phi' + fps f'] d / r,
+// fps = F'(rho_i) + F'(rho_j).
+template <int MODE>
+__device__ __forceinline__ void eam_pair(const float (&xi)[3], const float4 pj, float fps, const EamConst& k,
+                                         const float4* __restrict__ rtab, float& rho, float& e,
+                                         float (&g)[3]) {
+    const float pjv[3] = {pj.x, pj.y, pj.z};
+    float d[3];
+    int lo[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float v = xi[a] - pjv[a];
+        v = v - k.lf[a] * rintf(v * k.il[a]);
+        d[a] = v;
+        lo[a] = max((int)ceilf((-k.rcp - v) * k.il[a] - 1e-4f), -k.ns[a]);
+    }
+    for (int kx = 0; kx < k.ks[0]; ++kx) {
+        const int sx = lo[0] + kx;
+        const float dx = d[0] + (float)sx * k.lf[0];
+        const float dx2 = dx * dx;
+        for (int ky = 0; ky < k.ks[1]; ++ky) {
+            const int sy = lo[1] + ky;
+            const float dy = d[1] + (float)sy * k.lf[1];
+            const float dxy2 = dx2 + dy * dy;
+            const bool okxy = sx <= k.ns[0] && sy <= k.ns[1];
+            for (int kz = 0; kz < k.ks[2]; ++kz) {
+                const int sz = lo[2] + kz;
+                const float dz = d[2] + (float)sz * k.lf[2];
+                const float r2 = dxy2 + dz * dz;
+                if (!(okxy && sz <= k.ns[2] && r2 <= k.rc2p)) continue;
+                const float r = sqrtf(r2);
+                if (!(r > 0.0f && r <= k.rc)) continue;  // r == 0: the atom itself, or a coincident one
+                const float t = r * k.inv_dr;
+                const int m = min((int)t, k.nr2);
+                const float p = fminf(t - (float)m, 1.0f);
+                const float4 qf = rtab[2 * m];
+                if (MODE == 1) {
+                    rho += eam_cubic(qf, p);
+                    continue;
+                }
+                const float4 qz = rtab[2 * m + 1];
+                const float inv = 1.0f / r;
+                const float phi = eam_cubic(qz, p) * inv;
+                if (MODE == 0) {
+                    rho += eam_cubic(qf, p);
+                    e += phi;
+                } else {
+                    const float dphi = (eam_dcubic(qz, p) * k.inv_dr - phi) * inv;
+                    const float w = (dphi + fps * (eam_dcubic(qf, p) * k.inv_dr)) * inv;
+                    g[0] += w * dx;
+                    g[1] += w * dy;
+                    g[2] += w * dz;
+                }
+            }
+        }
+    }
+}
+
+inline int eam_const(EamConst& k, int nr, double dr, int nrho, double drho, double f_end, double fp_end,
+                     double lx, double ly, double lz, double rc) {
+    const double L[3] = {lx, ly, lz};
+    if (nr < 2 || nrho < 2 || !(dr > 0.0) || !(drho > 0.0) || !(rc > 0.0)) return 1;
+    const double rcp = rc * (1.0 + 1e-5);
+    for (int a = 0; a < 3; ++a) {
+        if (!(L[a] > 0.0) || rc / L[a] > 8.0) return 1;
+        k.lf[a] = (float)L[a];
+        k.il[a] = (float)(1.0 / L[a]);
+        k.ns[a] = (int)std::floor(rc / L[a] + 0.5);
+        const int span = (int)std::floor(2.0 * rcp / L[a] + 2e-4) + 1;
+        k.ks[a] = span < 2 * k.ns[a] + 1 ? span : 2 * k.ns[a] + 1;
+    }
+    k.rc = (float)rc;
+    k.rcp = (float)rcp;
+    k.rc2p = (float)(rcp * rcp);
+    k.inv_dr = (float)(1.0 / dr);
+    k.inv_drho = (float)(1.0 / drho);
+    k.rho_max = (float)((nrho - 1) * drho);
+    k.f_end = (float)f_end;
+    k.fp_end = (float)fp_end;
+    k.nr2 = nr - 2;
+    k.nrho2 = nrho - 2;
+    return 0;
+}
+
 }  // namespace
 
 #endif  // NFK_SYSTEMS_DEV_H_

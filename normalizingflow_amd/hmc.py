@@ -3,7 +3,7 @@ nf/hmc.py), for one chain or C independent chains at once.
 
 ``HMC(simulation, ...)`` keeps the reference's constructor and its
 ``generate_v`` / ``run_sim`` / ``hmc`` methods.  ``init_pos`` is one
-configuration ([W]; ``LJ``: [n, dim]) -- one chain, with the reference's
+configuration ([W]; ``LJ``, ``EAM``: [n, dim]) -- one chain, with the reference's
 shapes -- or a batch ([C, W]; [C, n, dim]): C chains that share every launch.
 One epoch is one ``randn``, one trajectory launch (systems ``integration_step``),
 one ``rand`` and one Metropolis launch (nfk_hmc_accept); nothing in the loop
@@ -30,7 +30,7 @@ import torch
 from torch.distributions import MultivariateNormal
 
 from . import kernels as K_
-from .systems import LJ, _SCHEMES
+from .systems import EAM, LJ, _SCHEMES
 
 __all__ = ["HMC"]
 
@@ -89,7 +89,7 @@ class HMC:
         return x.device, x.dtype, chains, x.numel() == self.width and x.dim() <= self._single_dims()
 
     def _single_dims(self):
-        return 2 if isinstance(self.simulation, LJ) else 1  # LJ positions are [..., n, dim]
+        return 2 if isinstance(self.simulation, (LJ, EAM)) else 1  # their positions are [..., n, dim]
 
     def _var(self, device, dtype):
         """The velocities' variances, [W], kept per device: no copy inside the epoch loop."""

@@ -560,6 +560,45 @@ def lj_potential_bwd(x, g, gx, *, n, dim, boxlength, sigma=1.0, epsilon=1.0, cut
            n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
 
 
+def eam_supported(n):
+    return bool(_lib.load().nfk_eam_supported(n))
+
+
+def _eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc):
+    """The table and box arguments of nfk_eam_potential[_bwd].  rtab: [Nr - 1, 2, 4]
+    (f's and z's quadruples of an interval adjacent), ftab: [Nrho - 1, 4]."""
+    for t, name in ((rtab, "rtab"), (ftab, "ftab")):
+        if t.dtype != F32 or not t.is_contiguous() or t.shape[-1] != 4:
+            raise ValueError("%s must be a contiguous float32 tensor of quadruples" % name)
+    if rtab.dim() != 3 or rtab.shape[1] != 2 or ftab.dim() != 2:
+        raise ValueError("rtab must be [Nr - 1, 2, 4] and ftab [Nrho - 1, 4]")
+    lx, ly, lz = (float(v) for v in box)
+    return (rtab.data_ptr(), rtab.shape[0] + 1, float(dr), ftab.data_ptr(), ftab.shape[0] + 1, float(drho),
+            float(f_end), float(fp_end), lx, ly, lz, float(rc))
+
+
+def eam_potential(x, out, *, n, rtab, ftab, dr, drho, f_end, fp_end, box, rc):
+    """nfk_eam_potential.  x: [B, n*3] rows of n atoms."""
+    dev = _require_hip(x, out, rtab, ftab)
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    if x.shape[1] != n * 3:
+        raise ValueError("x must be [B, %d], got %s" % (n * 3, tuple(x.shape)))
+    _timed("nfk_eam_potential", dev, "nfk_eam_potential", xp, ldx, _vec(out, B, "out"), B, n,
+           *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
+
+
+def eam_potential_bwd(x, g, gx, *, n, rtab, ftab, dr, drho, f_end, fp_end, box, rc):
+    dev = _require_hip(x, g, gx, rtab, ftab)
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    gp, ldg = _mat(gx, "gx")
+    if x.shape[1] != n * 3 or gx.shape != x.shape:
+        raise ValueError("x and gx must be [B, %d]" % (n * 3))
+    _timed("nfk_eam_potential_bwd", dev, "nfk_eam_potential_bwd", xp, ldx, _vec(g, B, "g"), gp, ldg, B, n,
+           *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
+
+
 # ---------------------------------------------------------------------------
 # trajectories and the Metropolis step (nfk_dynamics.hip)
 def _traj_args(x_in, v_in, x_out, v_out, pot, width, path_len, dt, scheme):

@@ -17,8 +17,12 @@ what the Normal prior gets: the kernel with ``+ sign * log|det|`` fused, a
 status word for the reference's NaN ``ValueError``, an autograd node under
 training and HIP-graph capture (models._prior_log_prob).
 
-Out of scope: LAMMPS, Fe, MBAR and plotting.  HMC is in hmc.py, the BAR
-estimator in bar.py.
+``EAM`` is the Fe target without LAMMPS: the embedded-atom energy of a setfl
+table file (``read_setfl``) over every periodic image within the cutoff, by
+the kernels of nfk_eam.hip.
+
+Out of scope: LAMMPS itself and plotting.  HMC is in hmc.py, the BAR estimator
+in bar.py, MBAR in mbar.py.
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ from torch.autograd.function import once_differentiable
 from . import kernels as K_
 from .flows import check_status
 
-__all__ = ["EinsteinCrystal", "GaussianMixture", "LJ", "read_xyz", "load_position"]
+__all__ = ["EinsteinCrystal", "GaussianMixture", "LJ", "EAM", "read_xyz", "load_position", "read_setfl"]
 
 _LOG_2PI = math.log(2 * math.pi)
 
@@ -65,6 +69,60 @@ def read_xyz(path):
 def load_position(path):
     """utils.load_position: the frames of an XYZ file, [nframes, natoms * 3]."""
     return read_xyz(path).flatten(start_dim=1)
+
+
+def read_setfl(path):
+    """A single-element setfl table file (LAMMPS ``eam/alloy``; ``eam/fs`` has
+    the same layout for one element): 3 comment lines, ``Nelements name``,
+    ``Nrho drho Nr dr rc``, the element line, then Nrho values of F(rho), Nr of
+    f(r) and Nr of z(r) = r phi(r), free-format across lines.  Returns a dict
+    with ``nrho, drho, nr, dr, rc``, the fp64 arrays ``F, f, z``, ``element``
+    (its name) and ``element_line`` (the four tokens of the element line).
+    More than one element raises ``NotImplementedError``."""
+    with open(path) as fh:
+        lines = fh.read().splitlines()
+    if len(lines) < 6:
+        raise ValueError("%s: not a setfl file (%d lines)" % (path, len(lines)))
+    head = lines[3].split()
+    if int(head[0]) != 1:
+        raise NotImplementedError("%s: %s elements; only single-element setfl files are read" % (path, head[0]))
+    grid = lines[4].split()
+    nrho, drho, nr, dr, rc = int(grid[0]), _fnum(grid[1]), int(grid[2]), _fnum(grid[3]), _fnum(grid[4])
+    vals = np.array([_fnum(t) for ln in lines[6:] for t in ln.split()], dtype=np.float64)
+    if len(vals) < nrho + 2 * nr:
+        raise ValueError("%s: %d table values, expected %d" % (path, len(vals), nrho + 2 * nr))
+    return dict(element=head[1] if len(head) > 1 else "", element_line=lines[5].split(), nrho=nrho, drho=drho,
+                nr=nr, dr=dr, rc=rc, F=vals[:nrho].copy(), f=vals[nrho:nrho + nr].copy(),
+                z=vals[nrho + nr:nrho + 2 * nr].copy())
+
+
+def _fnum(tok):
+    return float(tok.replace("D", "E").replace("d", "e"))
+
+
+def _cubic_table(y):
+    """The C1 piecewise cubic through the nodes y (fp64, n >= 5): per interval
+    m the quadruple (c3, c4, s_m, y_m) of ((c3 p + c4) p + s_m) p + y_m on
+    p in [0, 1], with five-point node slopes inside and one- and two-sided
+    differences at the ends.  Returns ([n - 1, 4], the n node slopes)."""
+    y = np.asarray(y, dtype=np.float64)
+    n = len(y)
+    if n < 5:
+        raise ValueError("a table needs at least 5 points, got %d" % n)
+    s = np.empty(n)
+    s[0] = y[1] - y[0]
+    s[1] = (y[2] - y[0]) / 2
+    s[2:n - 2] = ((y[:n - 4] - y[4:]) + 8 * (y[3:n - 1] - y[1:n - 3])) / 12
+    s[n - 2] = (y[n - 1] - y[n - 3]) / 2
+    s[n - 1] = y[n - 1] - y[n - 2]
+    dy = y[1:] - y[:-1]
+    c4 = 3 * dy - 2 * s[:-1] - s[1:]
+    c3 = s[:-1] + s[1:] - 2 * dy
+    return np.stack((c3, c4, s[:-1], y[:-1]), axis=1), s
+
+
+def _cubic(q, p):
+    return ((q[..., 0] * p + q[..., 1]) * p + q[..., 2]) * p + q[..., 3]
 
 
 def _load_traj(src):
@@ -114,7 +172,7 @@ class _Dynamics:
     ``get_potential`` and ``integration_step``.
 
     A position is one configuration or a batch of independent ones, [W] or
-    [B, W] (``LJ``: [..., n, dim]).  The reference's own batch, one flattened
+    [B, W] (``LJ``, ``EAM``: [..., n, dim]).  The reference's own batch, one flattened
     vector of B configurations, gives the same numbers; results come back in
     the shape that was given, the potential as [B].
 
@@ -247,6 +305,25 @@ class _Dynamics:
                                     keep_force=True)
         self.position, self.velocity = x, v
         return x, pot
+
+
+class _SimData:
+    """The trajectory holder of the reference's SimData (systems.py:107-142):
+    ``traj`` [frames, ...] on ``self.device``, ``sample`` and ``update_data``."""
+
+    def sample(self, nsamples, flatten=True, random=True):
+        if random:
+            idx = torch.randint(len(self.traj), [nsamples]).to(self.traj.device)
+            samples = self.traj.index_select(0, idx)
+        else:
+            samples = self.traj[:nsamples]
+        return samples.reshape(nsamples, -1) if flatten else samples
+
+    def update_data(self, file, append=False):
+        """Replace the held trajectory by ``file``'s frames (a tensor, ``.npy``,
+        ``.pt`` or XYZ), or append them."""
+        traj = _load_traj(file).to(self.device)
+        self.traj = torch.cat((self.traj, traj.reshape(len(traj), *self.traj.shape[1:])), 0) if append else traj
 
 
 class _KernelBacked(_Dynamics):
@@ -545,7 +622,7 @@ class _LJFn(torch.autograd.Function):
         return gx, None, None, None
 
 
-class LJ(_Dynamics):
+class LJ(_SimData, _Dynamics):
     """systems.py:144-189: Lennard-Jones particles in a periodic cubic box,
     plus the trajectory holder of SimData (``sample``).  ``pos_dir`` may be a
     tensor, a ``.npy`` / ``.pt`` path or an XYZ file.
@@ -670,10 +747,216 @@ class LJ(_Dynamics):
         self._traj_nd = tuple(x.shape[-2:])
         return super()._integrate(x, v, path_len, dt, sch, keep_force)
 
-    def sample(self, nsamples, flatten=True, random=True):
-        if random:
-            idx = torch.randint(len(self.traj), [nsamples]).to(self.traj.device)
-            samples = self.traj.index_select(0, idx)
-        else:
-            samples = self.traj[:nsamples]
-        return samples.reshape(nsamples, -1) if flatten else samples
+
+# ---------------------------------------------------------------------------
+class _EAMFn(torch.autograd.Function):
+    """nfk_eam_potential on [B, n*3] rows, differentiable in x."""
+
+    @staticmethod
+    def forward(ctx, x, eam, n):
+        out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        K_.eam_potential(x, out, n=n, **eam._kw(x.device))
+        ctx.save_for_backward(x)
+        ctx.eam, ctx.n = eam, n
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        K_.eam_potential_bwd(x, g.contiguous(), gx, n=ctx.n, **ctx.eam._kw(x.device))
+        return gx, None, None
+
+
+class EAM(_SimData, _Dynamics):
+    """The Fe target of the reference (systems.py:225-253, a host loop that
+    hands one frame at a time to LAMMPS) as an embedded-atom model evaluated
+    here: N atoms of one species in a periodic orthorhombic box,
+
+        rho_i = sum_(j,s) f(r_ijs)
+        U     = sum_i F(rho_i) + 1/2 sum_i sum_(j,s) z(r_ijs) / r_ijs
+
+    with F, f and z = r phi from a setfl table (``table``: a path or the dict
+    ``read_setfl`` returns).  s runs over integer image shifts, r_ijs =
+    |x_i - x_j + s L|, and a term counts when 0 < r_ijs <= rc: every periodic
+    image inside the cutoff, not only the nearest (at the Fe configs' box the
+    cutoff exceeds L/2), self images (i == j, s != 0) included.  Each component
+    of x_i - x_j is wrapped once into [-L/2, L/2], then the shifts -n_a..n_a
+    with n_a = floor(rc / L_a + 0.5) are visited per axis.  Only exact r == 0
+    is skipped: the atom itself, and also a coincident atom, which therefore
+    contributes nothing (as LJ's ``d + (d == 0)`` does).
+
+    Each table becomes a C1 piecewise cubic in fp64 (``_cubic_table``; fp32
+    copies for the kernel): the interval index is clamped to the table, for r
+    the fraction p is clamped to 1, and beyond the last rho node F continues
+    as a straight line with the end slope.  The force is the exact gradient of
+    that interpolated energy.  To the best of our knowledge this is the scheme
+    of LAMMPS's ``pair_eam``; that could not be checked, so no bit parity with
+    LAMMPS is claimed.
+
+    ``potential(pos)``: [..., n, 3] -> [...].  fp32 device tensors take
+    nfk_eam.hip (one launch per batch, one for the gradient); CPU, fp64,
+    n > 256 and ``use_kernels = False`` take the plain-torch restatement in
+    the input's dtype, differentiable by autograd and chunked over rows.
+    ``boxlength`` is a scalar or (Lx, Ly, Lz).  The class also holds a
+    trajectory as the reference's SimData does (``sample``, ``update_data``).
+
+    Dynamics (``integration_step``, ``HMC``) is the per-step path on the force
+    kernel (``fused_dynamics = False``: the one-launch trajectory and HMC
+    kernels do not cover this system), in the unit-mass reduced time of every
+    other system here.  With a setfl table in LAMMPS metal units (eV,
+    Angstrom) one unit of that time is sqrt(m amu A^2 / eV) = 0.0101805
+    sqrt(m) ps for atoms of m g/mol, 0.076079 ps for Fe (55.845): a metal-units
+    timestep of 0.001 ps is dt = 0.013144 here, velocities are A per reduced
+    time, and beta = 1 / (8.617333e-5 eV/K * T)."""
+
+    use_kernels = True
+    fused_dynamics = False
+    _CHUNK_ELEMS = 1 << 21  # (i, j) pairs per chunk of the torch path
+
+    def __init__(self, table, boxlength, nparticles=None, pos_dir=None, device="cpu"):
+        self.device = device
+        tab = read_setfl(table) if isinstance(table, str) else table
+        self.table = tab
+        self.nr, self.dr, self.nrho, self.drho, self.rc = (int(tab["nr"]), float(tab["dr"]), int(tab["nrho"]),
+                                                           float(tab["drho"]), float(tab["rc"]))
+        if not (self.dr > 0 and self.drho > 0 and self.rc > 0):
+            raise ValueError("setfl spacings and cutoff must be positive")
+        if len(tab["F"]) != self.nrho or len(tab["f"]) != self.nr or len(tab["z"]) != self.nr:
+            raise ValueError("table lengths do not match nrho / nr")
+        self.boxlength = boxlength
+        box = np.broadcast_to(np.asarray(boxlength, dtype=np.float64), (3,))
+        self.box = tuple(float(v) for v in box)
+        if not all(v > 0 for v in self.box):
+            raise ValueError("box lengths must be positive, got %r" % (boxlength,))
+        self.nshift = tuple(int(math.floor(self.rc / v + 0.5)) for v in self.box)
+        qf, _ = _cubic_table(tab["f"])
+        qz, _ = _cubic_table(tab["z"])
+        qF, sF = _cubic_table(tab["F"])
+        self._rtab64 = torch.from_numpy(np.stack((qf, qz), axis=1))  # [nr - 1, 2, 4]
+        self._ftab64 = torch.from_numpy(qF)                          # [nrho - 1, 4]
+        self.rho_max = (self.nrho - 1) * self.drho
+        self.f_end = float(tab["F"][-1])
+        self.fp_end = float(sF[-1] / self.drho)
+        self._tabs_on = {}
+        self._nparticles = nparticles
+        if pos_dir is not None:
+            self.traj = _load_traj(pos_dir).to(device)
+
+    # ------------------------------------------------------------------ tables
+    def _tabs(self, device, dtype):
+        key = (torch.device(device), dtype)
+        if key not in self._tabs_on:
+            self._tabs_on[key] = (self._rtab64.to(device=device, dtype=dtype).contiguous(),
+                                  self._ftab64.to(device=device, dtype=dtype).contiguous())
+        return self._tabs_on[key]
+
+    def _kw(self, device):
+        rtab, ftab = self._tabs(device, torch.float32)
+        return dict(rtab=rtab, ftab=ftab, dr=self.dr, drho=self.drho, f_end=self.f_end, fp_end=self.fp_end,
+                    box=self.box, rc=self.rc)
+
+    def _kernel_ok(self, pos):
+        return (self.use_kernels and torch.is_tensor(pos) and pos.is_cuda and pos.dtype == torch.float32
+                and pos.dim() >= 2 and pos.shape[-1] == 3 and K_.eam_supported(pos.shape[-2]))
+
+    # ------------------------------------------------------------------ energy
+    def potential(self, pos):
+        if pos.dim() < 2 or pos.shape[-1] != 3:
+            raise ValueError("EAM positions are [..., n, 3]; got shape %s" % (tuple(pos.shape),))
+        n = pos.shape[-2]
+        if self._kernel_ok(pos):
+            x = _rows(pos, n * 3)
+            if torch.is_grad_enabled() and x.requires_grad:
+                out = _EAMFn.apply(x, self, n)
+            else:
+                out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+                K_.eam_potential(x.detach(), out, n=n, **self._kw(x.device))
+            return out.reshape(pos.shape[:-2])
+        rows = max(1, self._CHUNK_ELEMS // (n * n))
+        if pos.dim() < 3 or pos.shape[:-2].numel() <= rows:
+            return self._potential_torch(pos)
+        flat = pos.reshape(-1, n, 3)
+        out = torch.cat([self._potential_torch(flat[i:i + rows]) for i in range(0, flat.shape[0], rows)])
+        return out.reshape(pos.shape[:-2])
+
+    def _embed_torch(self, rho, ftab):
+        t = rho * (1.0 / self.drho)
+        m = t.detach().floor().clamp(0, self.nrho - 2)
+        inside = _cubic(ftab[m.long()], t - m)
+        return torch.where(rho < self.rho_max, inside, self.f_end + self.fp_end * (rho - self.rho_max))
+
+    def _potential_torch(self, pos):
+        """The definition in pos's dtype: a loop over the image shifts, each one
+        [..., n, n] pair terms; autograd gives the exact gradient of the
+        interpolated energy (dp/dr = 1/dr inside the table)."""
+        rtab, ftab = self._tabs(pos.device, pos.dtype)
+        d = pos.unsqueeze(-2) - pos.unsqueeze(-3)  # d[i, j] = x_i - x_j
+        comp = [d[..., a] - self.box[a] * torch.round(d[..., a] * (1.0 / self.box[a])) for a in range(3)]
+        rho = torch.zeros(pos.shape[:-1], dtype=pos.dtype, device=pos.device)
+        pair = torch.zeros_like(rho)
+        nx, ny, nz = self.nshift
+        inv_dr = 1.0 / self.dr
+        for sx in range(-nx, nx + 1):
+            dx = comp[0] + sx * self.box[0]
+            dx2 = dx * dx
+            for sy in range(-ny, ny + 1):
+                dy = comp[1] + sy * self.box[1]
+                dxy2 = dx2 + dy * dy
+                for sz in range(-nz, nz + 1):
+                    dz = comp[2] + sz * self.box[2]
+                    r2 = dxy2 + dz * dz
+                    nonzero = r2 > 0
+                    r = torch.sqrt(torch.where(nonzero, r2, torch.ones_like(r2)))
+                    ok = nonzero & (r <= self.rc)
+                    if not bool(ok.any()):
+                        continue
+                    r = torch.where(ok, r, torch.full_like(r, self.dr))  # any in-table value: masked below
+                    t = r * inv_dr
+                    m = t.detach().floor().clamp(max=self.nr - 2)
+                    p = (t - m).clamp(max=1.0)
+                    q = rtab[m.long()]
+                    zero = torch.zeros_like(r)
+                    rho = rho + torch.where(ok, _cubic(q[..., 0, :], p), zero).sum(-1)
+                    pair = pair + torch.where(ok, _cubic(q[..., 1, :], p) / r, zero).sum(-1)
+        return (self._embed_torch(rho, ftab) + 0.5 * pair).sum(-1)
+
+    def force(self, pos):
+        """-dU/dx, [..., n, 3]: the backward kernel on the device, autograd
+        through the torch path (row chunk by row chunk) elsewhere."""
+        n = pos.shape[-2]
+        if self._kernel_ok(pos):
+            x = _rows(pos.detach(), n * 3)
+            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            K_.eam_potential_bwd(x, torch.ones(x.shape[0], dtype=torch.float32, device=x.device), gx, n=n,
+                                 **self._kw(x.device))
+            return -gx.reshape(pos.shape)
+        flat = pos.detach().reshape(-1, n, 3)
+        rows = max(1, self._CHUNK_ELEMS // (n * n))
+        out = []
+        with torch.enable_grad():
+            for i in range(0, flat.shape[0], rows):
+                x = flat[i:i + rows].clone().requires_grad_()
+                u = self._potential_torch(x)
+                out.append(-torch.autograd.grad(u, x, torch.ones_like(u))[0])
+        return torch.cat(out).reshape(pos.shape)
+
+    def get_force(self, x):
+        return self.force(x)
+
+    @property
+    def nparticles(self):
+        if self._nparticles is not None:
+            return self._nparticles
+        if self.position is None:
+            raise AttributeError("EAM.nparticles needs nparticles=... or a held position")
+        return self.position.shape[-2]
+
+    def _hmc_ok(self, x_cur, shape):
+        return False  # nfk_hmc_run.hip does not cover this system
+
+    def _integrate(self, x, v, path_len, dt, sch, keep_force=False):
+        if x.dim() < 2 or x.shape[-1] != 3:
+            raise ValueError("EAM positions are [..., n, 3]; got shape %s" % (tuple(x.shape),))
+        return super()._integrate(x, v, path_len, dt, sch, keep_force)
