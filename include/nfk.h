@@ -724,6 +724,26 @@ int nfk_lj_trajectory(const float* x_in, int64_t ldxi, const float* v_in, int64_
                       int32_t path_len, double dt, double dt_sq, int32_t scheme, int32_t n, int32_t dim,
                       double boxlength, double sigma, double epsilon, int32_t has_cutoff, double cutoff,
                       int32_t shift, nfk_stream_t stream);
+/* nfk_eam_trajectory: the same contract for the embedded-atom model, rows of
+ * W = n*3.  Trajectory arguments as nfk_lj_trajectory, table and box arguments
+ * as nfk_eam_potential.  F = -(1.0f * gx) with gx of nfk_eam_potential_bwd at
+ * g = 1 and pot_out is nfk_eam_potential at x_out, the same device functions
+ * (nfk_systems_dev.h) in nfk_eam_potential's mapping and summation order: a
+ * launch equals, bit for bit in x, v AND pot_out, the chain of those kernels and
+ * elementwise fp32 ops it replaces.  x, v and the current force stay in
+ * registers; two LDS buffers per row (<= 32 KiB per block).  A force evaluation
+ * on a staged row is nfk_eam_potential_bwd's two (j, s) loops with F'(rho_j)
+ * left beside x_j in LDS and a barrier between them, so a step costs two
+ * barriers; all of them sit in block-uniform control flow.  Grid-stride over
+ * rows, at most 16,384 blocks.  Supported shapes: nfk_eam_supported(n).
+ * NFK_EINVAL, nothing launched: what nfk_lj_trajectory and nfk_eam_potential
+ * refuse. */
+int nfk_eam_trajectory(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out,
+                       int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out, int64_t batch,
+                       int32_t path_len, double dt, double dt_sq, int32_t scheme, int32_t n,
+                       const float* rtab, int32_t nr, double dr, const float* ftab, int32_t nrho,
+                       double drho, double f_end, double fp_end, double lx, double ly, double lz,
+                       double rc, nfk_stream_t stream);
 /* nfk_hmc_accept: chain c of `chains` accepts its proposal when
  *   r[c] < expf(((u_cur[c] - u_new[c]) [+ k_cur[c]) - k_new[c]] * (float)beta)
  * (accurate expf; k_cur and k_new are both null -- the reference's
@@ -801,6 +821,20 @@ int nfk_lj_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, co
                    int64_t chains, int32_t epochs, int32_t path_len, double dt, double dt_sq, int32_t scheme,
                    double beta, int32_t hamiltonian, int32_t n, int32_t dim, double boxlength, double sigma,
                    double epsilon, int32_t has_cutoff, double cutoff, int32_t shift, nfk_stream_t stream);
+/* nfk_eam_hmc_run: the same contract for the embedded-atom model: an epoch is
+ * nfk_eam_trajectory's arithmetic followed by nfk_hmc_accept's test, in
+ * nfk_lj_hmc_run's arrangement (x in registers, two LDS buffers per row, the
+ * unconditional restage after the decision).  Run arguments as nfk_lj_hmc_run,
+ * table and box arguments as nfk_eam_potential, which also names what is
+ * refused about them (checked before chains == 0 or epochs == 0 returns).
+ * nfk_eam_hmc_supported(n) == nfk_eam_supported(n). */
+int nfk_eam_hmc_supported(int32_t n);
+int nfk_eam_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, const float* v_draws,
+                    const float* r, float* v_last, int64_t ldv, float* pos_rec, float* pot_rec,
+                    int64_t chains, int32_t epochs, int32_t path_len, double dt, double dt_sq, int32_t scheme,
+                    double beta, int32_t hamiltonian, int32_t n, const float* rtab, int32_t nr, double dr,
+                    const float* ftab, int32_t nrho, double drho, double f_end, double fp_end, double lx,
+                    double ly, double lz, double rc, nfk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Bennett acceptance ratio (applications/src/bar.py:16-68), `problems`

@@ -215,6 +215,12 @@ SIGNATURES = {
         I64, I32, F64, F64, I32,        # batch, path_len, dt, dt_sq, scheme
         I32, I32,                       # n, dim
         F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_eam_trajectory": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, F64, F64, I32,        # batch, path_len, dt, dt_sq, scheme
+        I32,                            # n
+        P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
+        F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
     "nfk_hmc_accept": (ctypes.c_int, [
         P, I64, P, I64, P, P,           # x_cur, ldc, x_new, ldn, u_cur, u_new
         P, P, P, P,                     # k_cur, k_new, r, naccept
@@ -239,6 +245,14 @@ SIGNATURES = {
         F64, I32,                       # beta, hamiltonian
         I32, I32,                       # n, dim
         F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_eam_hmc_supported": (ctypes.c_int, [I32]),
+    "nfk_eam_hmc_run": (ctypes.c_int, [
+        P, I64, P, P, P, P, P, I64, P, P,   # x_cur, ldx, u_cur, naccept, v_draws, r, v_last, ldv, pos_rec, pot_rec
+        I64, I32, I32, F64, F64, I32,   # chains, epochs, path_len, dt, dt_sq, scheme
+        F64, I32,                       # beta, hamiltonian
+        I32,                            # n
+        P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
+        F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
     "nfk_bar_stage_cap": (ctypes.c_int, []),
     "nfk_bar": (ctypes.c_int, [
         P, I64, P, I64,                 # w_f, n_f, w_r, n_r

@@ -202,6 +202,98 @@ __global__ __launch_bounds__(256) void k_lj_traj(const float* x_in, int64_t ldxi
 }
 
 // ---------------------------------------------------------------------------
+// Embedded-atom model: k_eam's mapping and k_lj_traj's two LDS buffers per row.
+// A force evaluation on a staged buffer is two (j, s) loops with a barrier between
+// them (eam_row_step_force: the densities, F'(rho_i) into the .w of the lane's own
+// slots, the barrier, the forces), so a step has two barriers: that one and the
+// one after the new positions are staged in the other buffer, which was last read
+// before the previous step's staging barrier.  path_len and the scheme are
+// kernel-uniform and rows past `batch` walk the barriers without touching
+// memory: every __syncthreads sits in block-uniform control flow.
+// ---------------------------------------------------------------------------
+template <int G, int PPL>
+__global__ __launch_bounds__(256) void k_eam_traj(const float* x_in, int64_t ldxi, const float* v_in,
+                                                  int64_t ldvi, float* x_out, int64_t ldxo, float* v_out,
+                                                  int64_t ldvo, float* __restrict__ pot, int64_t batch,
+                                                  int n, Step s, const float4* __restrict__ rtab,
+                                                  const float4* __restrict__ ftab, EamConst k) {
+    extern __shared__ __attribute__((aligned(16))) float4 s_pos[];
+    constexpr int RPW = 64 / G, RPB = 4 * RPW;
+    const int lane = threadIdx.x & 63;
+    const int rb = (threadIdx.x >> 6) * RPW + lane / G;  // row within the block
+    const int c0 = lane % G;
+    float4* srow = s_pos + (size_t)rb * n;  // buffer 0; buffer 1 lies RPB rows further on
+    const int other = RPB * n;
+    for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < batch; r0 += (int64_t)gridDim.x * RPB) {
+        const int64_t b = r0 + rb;
+        const bool ok = b < batch;
+        float x[PPL][3], v[PPL][3], F[PPL][3], xn[PPL][3], Fn[PPL][3];
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+            const int i = c0 + q * G;
+            x[q][0] = x[q][1] = x[q][2] = 0.0f;
+            v[q][0] = v[q][1] = v[q][2] = 0.0f;
+            if (ok && i < n) {
+                const float* px = x_in + b * ldxi + (int64_t)i * 3;
+                const float* pv = v_in + b * ldvi + (int64_t)i * 3;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    x[q][d] = px[d];
+                    v[q][d] = pv[d];
+                }
+                srow[i] = make_float4(x[q][0], x[q][1], x[q][2], 0.0f);
+            }
+        }
+        __syncthreads();
+        int cur = 0;
+        eam_row_step_force<G, PPL>(ok, x, srow, n, c0, k, rtab, ftab, F);
+        for (int st = 0; st < s.path_len; ++st) {
+#pragma unroll
+            for (int q = 0; q < PPL; ++q)
+#pragma unroll
+                for (int d = 0; d < 3; ++d) xn[q][d] = step_x(x[q][d], v[q][d], F[q][d], s);
+            if (!s.verlet) eam_row_step_force<G, PPL>(ok, x, srow + cur * other, n, c0, k, rtab, ftab, Fn);
+#pragma unroll
+            for (int q = 0; q < PPL; ++q) {
+                const int i = c0 + q * G;
+                if (ok && i < n) srow[(cur ^ 1) * other + i] = make_float4(xn[q][0], xn[q][1], xn[q][2], 0.0f);
+            }
+            __syncthreads();
+            cur ^= 1;
+            if (s.verlet) eam_row_step_force<G, PPL>(ok, xn, srow + cur * other, n, c0, k, rtab, ftab, Fn);
+#pragma unroll
+            for (int q = 0; q < PPL; ++q)
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    v[q][d] = step_v(v[q][d], F[q][d], Fn[q][d], s);
+                    x[q][d] = xn[q][d];
+                    F[q][d] = Fn[q][d];
+                }
+        }
+        float e = 0.0f;
+        if (ok) {
+            e = eam_row_energy<G, PPL>(x, srow + cur * other, n, c0, k, rtab, ftab);
+#pragma unroll
+            for (int q = 0; q < PPL; ++q) {
+                const int i = c0 + q * G;
+                if (i < n) {
+                    float* px = x_out + b * ldxo + (int64_t)i * 3;
+                    float* pv = v_out + b * ldvo + (int64_t)i * 3;
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        px[d] = x[q][d];
+                        pv[d] = v[q][d];
+                    }
+                }
+            }
+        }
+        e = group_sum<G>(e);
+        if (ok && c0 == 0) pot[b] = e;
+        __syncthreads();  // the next round overwrites the staged rows
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Metropolis step: a chain on W lanes; the group's first lane decides and
 // updates the chain's scalars, the group copies the row.
 // ---------------------------------------------------------------------------
@@ -369,6 +461,48 @@ extern "C" int nfk_lj_trajectory(const float* x_in, int64_t ldxi, const float* v
 #undef LJ_CALL
 #undef LJ_CALL2
     return launch_status("nfk_lj_trajectory");
+}
+
+extern "C" int nfk_eam_trajectory(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi,
+                                  float* x_out, int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out,
+                                  int64_t batch, int32_t path_len, double dt, double dt_sq, int32_t scheme,
+                                  int32_t n, const float* rtab, int32_t nr, double dr, const float* ftab,
+                                  int32_t nrho, double drho, double f_end, double fp_end, double lx,
+                                  double ly, double lz, double rc, nfk_stream_t stream) {
+    if (!nfk_eam_supported(n)) return nfk_set_error("nfk_eam_trajectory: shape not supported");
+    if (check_traj("nfk_eam_trajectory", x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out, batch,
+                   (int64_t)n * 3, path_len, scheme))
+        return NFK_EINVAL;
+    EamConst k;
+    if (eam_setup("nfk_eam_trajectory", k, rtab, nr, dr, ftab, nrho, drho, f_end, fp_end, lx, ly, lz, rc))
+        return NFK_EINVAL;
+    if (batch == 0) return 0;
+    if (!rtab || !ftab) return nfk_set_error("nfk_eam_trajectory: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const Step s = make_step(path_len, dt, dt_sq, scheme);
+    const int G = lanes_for(n);
+    const int ppl = (n + 63) / 64;
+    const int rpb = 4 * (64 / G);
+    int64_t grid = (batch + rpb - 1) / rpb;
+    if (grid > 16384) grid = 16384;
+    const size_t lds = (size_t)2 * rpb * n * sizeof(float4);  // two buffers per row, <= 32 KiB (n <= 256)
+#define EAM_CALL2(GG, PP)                                                                                   \
+    hipLaunchKernelGGL((k_eam_traj<GG, PP>), dim3((unsigned)grid), dim3(256), lds, st, x_in, ldxi, v_in, ldvi, \
+                       x_out, ldxo, v_out, ldvo, pot_out, batch, n, s, (const float4*)rtab,                 \
+                       (const float4*)ftab, k)
+#define EAM_CALL(W) EAM_CALL2(W, 1)
+    if (ppl <= 1) {
+        NFK_W_DISPATCH(G, EAM_CALL)
+    } else if (ppl == 2) {
+        EAM_CALL2(64, 2);
+    } else if (ppl == 3) {
+        EAM_CALL2(64, 3);
+    } else {
+        EAM_CALL2(64, 4);
+    }
+#undef EAM_CALL
+#undef EAM_CALL2
+    return launch_status("nfk_eam_trajectory");
 }
 
 extern "C" int nfk_hmc_accept(float* x_cur, int64_t ldc, const float* x_new, int64_t ldn, float* u_cur,

@@ -390,7 +390,152 @@ __global__ __launch_bounds__(256) void k_lj_hmc(HmcRun a, int n, Step s, LjConst
     }
 }
 
-// Host checks shared by the three entry points; `shape_ok` is the system's
+// ---------------------------------------------------------------------------
+// Embedded-atom model: k_eam_traj's mapping and arithmetic (two LDS buffers per
+// row, eam_row_step_force with its barrier between the density and the force
+// loop) inside k_lj_hmc's epoch loop: x_cur, u and the count on chip, the
+// unconditional restage of x_cur after the decision.  epochs, path_len and the
+// scheme are kernel-uniform, so every __syncthreads sits in block-uniform
+// control flow; rows past `chains` walk the barriers without touching memory.
+// ---------------------------------------------------------------------------
+template <int G, int PPL>
+__global__ __launch_bounds__(256) void k_eam_hmc(HmcRun a, int n, Step s, const float4* __restrict__ rtab,
+                                                 const float4* __restrict__ ftab, EamConst k) {
+    extern __shared__ __attribute__((aligned(16))) float4 s_pos[];
+    constexpr int RPW = 64 / G, RPB = 4 * RPW;
+    const int lane = threadIdx.x & 63;
+    const int rb = (threadIdx.x >> 6) * RPW + lane / G;  // row within the block
+    const int c0 = lane % G;
+    const int64_t width = (int64_t)n * 3;
+    float4* srow = s_pos + (size_t)rb * n;  // buffer 0; buffer 1 lies RPB rows further on
+    const int other = RPB * n;
+    for (int64_t r0 = (int64_t)blockIdx.x * RPB; r0 < a.chains; r0 += (int64_t)gridDim.x * RPB) {
+        const int64_t b = r0 + rb;
+        const bool ok = b < a.chains;
+        float xc[PPL][3], x[PPL][3], v[PPL][3], F[PPL][3], xn[PPL][3], Fn[PPL][3];
+        float u = 0.0f;
+        int nacc = 0;
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+            const int i = c0 + q * G;
+            xc[q][0] = xc[q][1] = xc[q][2] = 0.0f;
+            v[q][0] = v[q][1] = v[q][2] = 0.0f;
+            if (ok && i < n) {
+                const float* px = a.x_cur + b * a.ldx + (int64_t)i * 3;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) xc[q][d] = px[d];
+                srow[i] = make_float4(xc[q][0], xc[q][1], xc[q][2], 0.0f);
+            }
+        }
+        if (ok) u = a.u_cur[b];
+        __syncthreads();
+        int cur = 0;
+        for (int e = 0; e < a.epochs; ++e) {
+            const int64_t ec = (int64_t)e * a.chains + b;
+            float kc = 0.0f, kn = 0.0f;
+#pragma unroll
+            for (int q = 0; q < PPL; ++q) {
+                const int i = c0 + q * G;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    x[q][d] = xc[q][d];
+                    v[q][d] = 0.0f;
+                }
+                if (ok && i < n) {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        if (a.pos_rec != nullptr) a.pos_rec[ec * width + (int64_t)i * 3 + d] = xc[q][d];
+                        v[q][d] = a.v_draws[ec * width + (int64_t)i * 3 + d];
+                        kc += v[q][d] * v[q][d];
+                    }
+                }
+            }
+            eam_row_step_force<G, PPL>(ok, x, srow + cur * other, n, c0, k, rtab, ftab, F);
+            for (int st = 0; st < s.path_len; ++st) {
+#pragma unroll
+                for (int q = 0; q < PPL; ++q)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) xn[q][d] = step_x(x[q][d], v[q][d], F[q][d], s);
+                if (!s.verlet) eam_row_step_force<G, PPL>(ok, x, srow + cur * other, n, c0, k, rtab, ftab, Fn);
+#pragma unroll
+                for (int q = 0; q < PPL; ++q) {
+                    const int i = c0 + q * G;
+                    if (ok && i < n)
+                        srow[(cur ^ 1) * other + i] = make_float4(xn[q][0], xn[q][1], xn[q][2], 0.0f);
+                }
+                __syncthreads();
+                cur ^= 1;
+                if (s.verlet) eam_row_step_force<G, PPL>(ok, xn, srow + cur * other, n, c0, k, rtab, ftab, Fn);
+#pragma unroll
+                for (int q = 0; q < PPL; ++q)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        v[q][d] = step_v(v[q][d], F[q][d], Fn[q][d], s);
+                        x[q][d] = xn[q][d];
+                        F[q][d] = Fn[q][d];
+                    }
+            }
+            float en = 0.0f;
+            if (ok) en = eam_row_energy<G, PPL>(x, srow + cur * other, n, c0, k, rtab, ftab);
+            const float un = group_sum<G>(en);
+            if (a.hamiltonian) {
+#pragma unroll
+                for (int q = 0; q < PPL; ++q) {
+                    if (ok && c0 + q * G < n) {
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) kn += v[q][d] * v[q][d];
+                    }
+                }
+                kc = group_sum<G>(kc) * 0.5f;
+                kn = group_sum<G>(kn) * 0.5f;
+            }
+            int acc = 0;
+            if (ok && c0 == 0) {
+                if (a.pot_rec != nullptr) a.pot_rec[ec] = u;
+                acc = hmc_decide(u, un, kc, kn, a.r[ec], a.beta, a.hamiltonian);
+            }
+            acc = __shfl(acc, lane - c0, 64);
+            if (acc) {
+                u = un;
+                nacc += 1;
+#pragma unroll
+                for (int q = 0; q < PPL; ++q)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) xc[q][d] = x[q][d];
+            }
+            // the next epoch starts from x_cur, accepted or not
+#pragma unroll
+            for (int q = 0; q < PPL; ++q) {
+                const int i = c0 + q * G;
+                if (ok && i < n) srow[(cur ^ 1) * other + i] = make_float4(xc[q][0], xc[q][1], xc[q][2], 0.0f);
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        if (ok) {
+#pragma unroll
+            for (int q = 0; q < PPL; ++q) {
+                const int i = c0 + q * G;
+                if (i < n) {
+                    float* px = a.x_cur + b * a.ldx + (int64_t)i * 3;
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        px[d] = xc[q][d];
+                        if (a.v_last != nullptr) a.v_last[b * a.ldv + (int64_t)i * 3 + d] = v[q][d];
+                    }
+                }
+            }
+            if (c0 == 0) {
+                a.u_cur[b] = u;
+                if (a.naccept != nullptr) a.naccept[b] += nacc;
+            }
+        }
+        // the next round's first stage writes buffer 0; every read of this round
+        // came before the last epoch's barrier
+    }
+}
+
+// Host checks shared by the entry points; `shape_ok` is the system's
 // *_hmc_supported answer.  Returns 0 to go on, 1 to return 0 without a launch,
 // NFK_EINVAL after nfk_set_error.
 int check_run(const char* who, const void* x_cur, int64_t ldx, const void* u_cur, const void* v_draws,
@@ -448,6 +593,8 @@ extern "C" int nfk_gmix_hmc_supported(int32_t npart, int32_t dim, int32_t ncente
 }
 
 extern "C" int nfk_lj_hmc_supported(int32_t n, int32_t dim) { return nfk_lj_supported(n, dim); }
+
+extern "C" int nfk_eam_hmc_supported(int32_t n) { return nfk_eam_supported(n); }
 
 extern "C" int nfk_einstein_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept,
                                     const float* v_draws, const float* r, float* v_last, int64_t ldv,
@@ -584,4 +731,48 @@ extern "C" int nfk_lj_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* 
 #undef LJ_CALL
 #undef LJ_CALL2
     return launch_status("nfk_lj_hmc_run");
+}
+
+extern "C" int nfk_eam_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, const float* v_draws,
+                               const float* r, float* v_last, int64_t ldv, float* pos_rec, float* pot_rec,
+                               int64_t chains, int32_t epochs, int32_t path_len, double dt, double dt_sq,
+                               int32_t scheme, double beta, int32_t hamiltonian, int32_t n, const float* rtab,
+                               int32_t nr, double dr, const float* ftab, int32_t nrho, double drho,
+                               double f_end, double fp_end, double lx, double ly, double lz, double rc,
+                               nfk_stream_t stream) {
+    const int shape_ok = nfk_eam_hmc_supported(n);
+    EamConst k;
+    if (shape_ok &&
+        eam_setup("nfk_eam_hmc_run", k, rtab, nr, dr, ftab, nrho, drho, f_end, fp_end, lx, ly, lz, rc))
+        return NFK_EINVAL;
+    const int rcode = check_run("nfk_eam_hmc_run", x_cur, ldx, u_cur, v_draws, r, v_last, ldv, pos_rec, pot_rec,
+                                chains, epochs, path_len, scheme, shape_ok ? (int64_t)n * 3 : 0, shape_ok);
+    if (rcode != 0) return rcode == 1 ? 0 : rcode;
+    if (!rtab || !ftab) return nfk_set_error("nfk_eam_hmc_run: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const HmcRun a = make_run(x_cur, ldx, u_cur, naccept, v_draws, r, v_last, ldv, pos_rec, pot_rec, chains,
+                              epochs, beta, hamiltonian);
+    const Step s = make_step(path_len, dt, dt_sq, scheme);
+    const int G = lanes_for(n);
+    const int ppl = (n + 63) / 64;
+    const int rpb = 4 * (64 / G);
+    int64_t grid = (chains + rpb - 1) / rpb;
+    if (grid > 16384) grid = 16384;
+    const size_t lds = (size_t)2 * rpb * n * sizeof(float4);  // two buffers per row, <= 32 KiB (n <= 256)
+#define EAM_CALL2(GG, PP)                                                                              \
+    hipLaunchKernelGGL((k_eam_hmc<GG, PP>), dim3((unsigned)grid), dim3(256), lds, st, a, n, s,         \
+                       (const float4*)rtab, (const float4*)ftab, k)
+#define EAM_CALL(W) EAM_CALL2(W, 1)
+    if (ppl <= 1) {
+        NFK_W_DISPATCH(G, EAM_CALL)
+    } else if (ppl == 2) {
+        EAM_CALL2(64, 2);
+    } else if (ppl == 3) {
+        EAM_CALL2(64, 3);
+    } else {
+        EAM_CALL2(64, 4);
+    }
+#undef EAM_CALL
+#undef EAM_CALL2
+    return launch_status("nfk_eam_hmc_run");
 }

@@ -320,6 +320,100 @@ __device__ __forceinline__ void eam_pair(const float (&xi)[3], const float4 pj, 
     }
 }
 
+// The (j, s) loops of a row in k_eam's mapping (nfk_eam.hip): lane c0 of a group of
+// G lanes owns atoms c0 + q G, q < PPL, in xi; srow holds the row's n atoms as
+// float4, read by broadcast, j outermost.  The expressions and the summation order
+// are k_eam's, so a force inside a trajectory has the bits of the backward kernel's.
+// rho_i of the lane's atoms.
+template <int G, int PPL>
+__device__ __forceinline__ void eam_row_density(const float (&xi)[PPL][3], const float4* srow, int n, int c0,
+                                                const EamConst& k, const float4* __restrict__ rtab,
+                                                float (&rho)[PPL]) {
+    float e[PPL], f[PPL][3];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) rho[q] = e[q] = f[q][0] = f[q][1] = f[q][2] = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = srow[j];
+#pragma unroll
+        for (int q = 0; q < PPL; ++q)
+            if (c0 + q * G < n) eam_pair<1>(xi[q], pj, 0.0f, k, rtab, rho[q], e[q], f[q]);
+    }
+}
+
+// dU/dx_i of the lane's atoms in f, given F'(rho_i) in fpi and F'(rho_j) in the .w
+// of the staged slots.  j == i is skipped: the self images' r does not depend on x_i.
+template <int G, int PPL>
+__device__ __forceinline__ void eam_row_force(const float (&xi)[PPL][3], const float (&fpi)[PPL],
+                                              const float4* srow, int n, int c0, const EamConst& k,
+                                              const float4* __restrict__ rtab, float (&f)[PPL][3]) {
+    float rho[PPL], e[PPL];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) rho[q] = e[q] = f[q][0] = f[q][1] = f[q][2] = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = srow[j];
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+            const int i = c0 + q * G;
+            if (i < n && i != j) eam_pair<2>(xi[q], pj, fpi[q] + pj.w, k, rtab, rho[q], e[q], f[q]);
+        }
+    }
+}
+
+// The lane's share of the row's energy, sum_q F(rho_q) + 0.5 e_q; the row's is its
+// group_sum<G>.
+template <int G, int PPL>
+__device__ __forceinline__ float eam_row_energy(const float (&xi)[PPL][3], const float4* srow, int n, int c0,
+                                                const EamConst& k, const float4* __restrict__ rtab,
+                                                const float4* __restrict__ ftab) {
+    float rho[PPL], e[PPL], f[PPL][3];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) rho[q] = e[q] = f[q][0] = f[q][1] = f[q][2] = 0.0f;
+    for (int j = 0; j < n; ++j) {
+        const float4 pj = srow[j];
+#pragma unroll
+        for (int q = 0; q < PPL; ++q)
+            if (c0 + q * G < n) eam_pair<0>(xi[q], pj, 0.0f, k, rtab, rho[q], e[q], f[q]);
+    }
+    float u = 0.0f;
+#pragma unroll
+    for (int q = 0; q < PPL; ++q)
+        if (c0 + q * G < n) u += eam_embed<false>(rho[q], ftab, k) + 0.5f * e[q];
+    return u;
+}
+
+// The integrator's force on the lane's atoms, F = -(1.0f * dU/dx) (what EAM.force makes
+// of the backward kernel at g = 1), from the row staged in srow: the density loop,
+// F'(rho_i) left in the .w of the lane's own slots, a barrier, the force loop.  The
+// __syncthreads is unconditional, so every call sits in block-uniform control flow;
+// a row with ok == false walks the barrier without touching memory and gets zeros.
+template <int G, int PPL>
+__device__ __forceinline__ void eam_row_step_force(bool ok, const float (&xi)[PPL][3], float4* srow, int n,
+                                                   int c0, const EamConst& k,
+                                                   const float4* __restrict__ rtab,
+                                                   const float4* __restrict__ ftab, float (&F)[PPL][3]) {
+    float rho[PPL], fpi[PPL], f[PPL][3];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) rho[q] = 0.0f;
+    if (ok) eam_row_density<G, PPL>(xi, srow, n, c0, k, rtab, rho);
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        const int i = c0 + q * G;
+        fpi[q] = 0.0f;
+        if (ok && i < n) {
+            fpi[q] = eam_embed<true>(rho[q], ftab, k);
+            reinterpret_cast<float*>(srow + i)[3] = fpi[q];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) f[q][0] = f[q][1] = f[q][2] = 0.0f;
+    if (ok) eam_row_force<G, PPL>(xi, fpi, srow, n, c0, k, rtab, f);
+#pragma unroll
+    for (int q = 0; q < PPL; ++q)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) F[q][d] = ok ? -(1.0f * f[q][d]) : 0.0f;
+}
+
 inline int eam_const(EamConst& k, int nr, double dr, int nrho, double drho, double f_end, double fp_end,
                      double lx, double ly, double lz, double rc) {
     const double L[3] = {lx, ly, lz};
@@ -344,6 +438,20 @@ inline int eam_const(EamConst& k, int nr, double dr, int nrho, double drho, doub
     k.nr2 = nr - 2;
     k.nrho2 = nrho - 2;
     return 0;
+}
+
+// The table and box checks of nfk_eam_potential for the dynamics entry points: 0 with k
+// filled, or NFK_EINVAL after nfk_set_error.
+inline int eam_setup(const char* who, EamConst& k, const void* rtab, int nr, double dr, const void* ftab,
+                     int nrho, double drho, double f_end, double fp_end, double lx, double ly, double lz,
+                     double rc) {
+    char buf[120];
+    const char* why = nullptr;
+    if ((((uintptr_t)rtab) | ((uintptr_t)ftab)) & 15) why = "tables need 16-byte alignment";
+    else if (eam_const(k, nr, dr, nrho, drho, f_end, fp_end, lx, ly, lz, rc)) why = "bad tables, box or cutoff";
+    if (!why) return 0;
+    std::snprintf(buf, sizeof(buf), "%s: %s", who, why);
+    return nfk_set_error(buf);
 }
 
 }  // namespace

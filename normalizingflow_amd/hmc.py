@@ -11,6 +11,12 @@ waits for the device and nothing is printed.  On the CPU, in fp64 or with the
 simulation's ``use_kernels`` or ``fused_dynamics`` switched off the same steps
 run as torch ops.  ``hmc(..., one_launch=True)`` draws the random numbers of
 many epochs in bulk and runs all of them in ONE launch (nfk_hmc_run.hip).
+``EAM`` takes the same kernels (nfk_eam_trajectory up to 6,144 chains per
+launch, the per-step force path above that; nfk_eam_hmc_run), so its
+per-epoch Metropolis step is nfk_hmc_accept too, whose ``expf`` may decide an
+exact near-tie differently from ``torch.exp``.  At the Fe shape a trajectory is
+one wave's serial force loop in either form: the launch saves 1-7 % up to
+6,144 rows and nothing on ``hmc(500)``.
 
 As in the reference the default test accepts on the potential alone,
 ``exp((U_old - U_new) * beta)`` (hmc.py:56), and the default integrator is the

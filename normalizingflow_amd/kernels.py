@@ -646,6 +646,15 @@ def lj_trajectory(x_in, v_in, x_out, v_out, pot, *, path_len, dt, scheme, n, dim
            *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
 
 
+def eam_trajectory(x_in, v_in, x_out, v_out, pot, *, path_len, dt, scheme, n, rtab, ftab, dr, drho, f_end,
+                   fp_end, box, rc):
+    """nfk_eam_trajectory.  Rows are [n*3]; tables and box as ``eam_potential``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, rtab, ftab)
+    _timed("nfk_eam_trajectory", dev, "nfk_eam_trajectory",
+           *_traj_args(x_in, v_in, x_out, v_out, pot, n * 3, path_len, dt, scheme), n,
+           *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
+
+
 def hmc_accept(x_cur, x_new, u_cur, u_new, r, naccept, *, beta, k_cur=None, k_new=None):
     """nfk_hmc_accept: the Metropolis step over the rows of x_cur, in place."""
     dev = _require_hip(x_cur, x_new, u_cur, u_new, r, naccept, k_cur, k_new)
@@ -672,6 +681,10 @@ def gmix_hmc_supported(npart, dim, ncenters):
 
 def lj_hmc_supported(n, dim):
     return bool(_lib.load().nfk_lj_hmc_supported(n, dim))
+
+
+def eam_hmc_supported(n):
+    return bool(_lib.load().nfk_eam_hmc_supported(n))
 
 
 def _hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, width, path_len, dt, scheme,
@@ -737,6 +750,17 @@ def lj_hmc_run(x_cur, u_cur, naccept, v_draws, r, *, path_len, dt, scheme, beta,
            *_hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, n * dim, path_len, dt,
                           scheme, beta, hamiltonian),
            n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
+
+
+def eam_hmc_run(x_cur, u_cur, naccept, v_draws, r, *, path_len, dt, scheme, beta, n, rtab, ftab, dr, drho, f_end,
+                fp_end, box, rc, hamiltonian=False, v_last=None, pos_rec=None, pot_rec=None):
+    """nfk_eam_hmc_run; rows are [n*3], tables and box as ``eam_potential``, other
+    arguments as ``einstein_hmc_run``."""
+    dev = _require_hip(x_cur, u_cur, naccept, v_draws, r, rtab, ftab, v_last, pos_rec, pot_rec)
+    _timed("nfk_eam_hmc_run", dev, "nfk_eam_hmc_run",
+           *_hmc_run_args(x_cur, u_cur, naccept, v_draws, r, v_last, pos_rec, pot_rec, n * 3, path_len, dt,
+                          scheme, beta, hamiltonian),
+           n, *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
 
 
 def bar_stage_cap():

@@ -802,18 +802,30 @@ class EAM(_SimData, _Dynamics):
     ``boxlength`` is a scalar or (Lx, Ly, Lz).  The class also holds a
     trajectory as the reference's SimData does (``sample``, ``update_data``).
 
-    Dynamics (``integration_step``, ``HMC``) is the per-step path on the force
-    kernel (``fused_dynamics = False``: the one-launch trajectory and HMC
-    kernels do not cover this system), in the unit-mass reduced time of every
-    other system here.  With a setfl table in LAMMPS metal units (eV,
+    Dynamics (``integration_step``, ``HMC``): fp32 device tensors with
+    n <= 256 take ONE launch per batch of trajectories (nfk_eam_trajectory) and
+    ``hmc(one_launch=True)`` one launch per run (nfk_eam_hmc_run), with the
+    bits of the per-step path in x, v, the potential and ``last_force``: the
+    kernels share the force and energy functions of nfk_eam.hip.  CPU, fp64,
+    n > 256, ``use_kernels = False`` and ``fused_dynamics = False`` run the
+    per-step path on the force kernel, and so do batches of more than 6,144
+    rows, where that path measured 1-10 % faster (at the Fe shape a row is one
+    wave's serial force loop in either form: the launch saves 1-7 % below the
+    cap and nothing on ``hmc(500)``).  The one observable difference from the
+    per-step torch ops: with ``fused_dynamics`` on, the per-epoch Metropolis
+    step is nfk_hmc_accept, as for the other systems, and its ``expf`` may
+    decide an exact near-tie differently from ``torch.exp``.  Timings: DESIGN.md
+    section 12.2.  Time is the unit-mass reduced time of every other system
+    here.  With a setfl table in LAMMPS metal units (eV,
     Angstrom) one unit of that time is sqrt(m amu A^2 / eV) = 0.0101805
     sqrt(m) ps for atoms of m g/mol, 0.076079 ps for Fe (55.845): a metal-units
     timestep of 0.001 ps is dt = 0.013144 here, velocities are A per reduced
     time, and beta = 1 / (8.617333e-5 eV/K * T)."""
 
     use_kernels = True
-    fused_dynamics = False
+    fused_dynamics = True
     _CHUNK_ELEMS = 1 << 21  # (i, j) pairs per chunk of the torch path
+    _FUSED_ROWS_MAX = 6144  # rows of one trajectory launch; above, the per-step path measured faster
 
     def __init__(self, table, boxlength, nparticles=None, pos_dir=None, device="cpu"):
         self.device = device
@@ -953,10 +965,29 @@ class EAM(_SimData, _Dynamics):
             raise AttributeError("EAM.nparticles needs nparticles=... or a held position")
         return self.position.shape[-2]
 
+    def _dyn_fused_ok(self, x, v):
+        # the bits are equal either way: the cap only picks the faster route
+        return super()._dyn_fused_ok(x, v) and x.shape[:-2].numel() <= self._FUSED_ROWS_MAX
+
+    def _dyn_rows(self, t):
+        return _rows(t, t.shape[-2] * 3)
+
+    def _dyn_pot_shape(self, pot, x):
+        return pot.reshape(x.shape[:-2])
+
+    def _trajectory(self, x, v, xo, vo, pot, path_len, dt, sch):
+        # the rows are [n*3]: _integrate notes n
+        K_.eam_trajectory(x, v, xo, vo, pot, path_len=path_len, dt=dt, scheme=sch, n=self._traj_n,
+                          **self._kw(x.device))
+
     def _hmc_ok(self, x_cur, shape):
-        return False  # nfk_hmc_run.hip does not cover this system
+        return self.use_kernels and len(shape) >= 2 and shape[-1] == 3 and K_.eam_hmc_supported(shape[-2])
+
+    def _hmc_launch(self, shape, x_cur, *args, **kw):
+        K_.eam_hmc_run(x_cur, *args, n=shape[-2], **self._kw(x_cur.device), **kw)
 
     def _integrate(self, x, v, path_len, dt, sch, keep_force=False):
         if x.dim() < 2 or x.shape[-1] != 3:
             raise ValueError("EAM positions are [..., n, 3]; got shape %s" % (tuple(x.shape),))
+        self._traj_n = x.shape[-2]
         return super()._integrate(x, v, path_len, dt, sch, keep_force)

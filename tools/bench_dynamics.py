@@ -26,6 +26,17 @@ alternating window by window:
   one_launch  ``hmc(500, one_launch=True)``: bulk draws and ONE nfk_*_hmc_run launch
   per_epoch   the default ``hmc(500)``: a trajectory and a Metropolis launch per
               epoch -- the code as it was before the one-launch kernels, the yardstick
+
+    python tools/bench_dynamics.py --kind eam [--hmc-run] [--out profiles/eam_dynamics_bench.json]
+
+is the same pair of measurements for systems.EAM at the Fe shape of
+tools/bench_eam.py (n = 54 perturbed bcc 3 x 3 x 3, rc = 0.61 L, 10^4-point
+tables): trajectories of 50, 500, 5,000, 6,144, 7,168 and 2^16 rows, one HMC
+epoch and, with --hmc-run, ``hmc(500)`` at 1 and 500 chains.  The fused side
+times nfk_eam_trajectory at every size: the row cap above which ``EAM`` itself
+takes the per-step path (``EAM._FUSED_ROWS_MAX``, set from these numbers) is
+lifted here.  Both invocations write into one file: sections the other one
+wrote are kept.
 """
 from __future__ import annotations
 
@@ -79,6 +90,10 @@ def systems_pair(kind, dev):
     for fused in (True, False):
         if kind == "lj":
             sim = systems.LJ(boxlength=L32, cutoff=1.6, device=dev)
+        elif kind == "eam":
+            tab, L = bench_eam().tables()
+            sim = systems.EAM(tab, L, device=dev)
+            sim._FUSED_ROWS_MAX = 1 << 62  # time the launch itself at every size: the class routes by this cap
         else:
             sim = systems.EinsteinCrystal(fcc32(), 3, boxlength=L32, alpha=600, device=dev)
         sim.fused_dynamics = fused
@@ -86,9 +101,31 @@ def systems_pair(kind, dev):
     return pair
 
 
+def bench_eam():
+    """tools/bench_eam.py as a module: the Fe shape's tables and constants."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import bench_eam as m
+    return m
+
+
+KT_FE = 0.00861733326  # the Fe configs' kT: velocities of sd sqrt(kT), beta = 1 / kT
+BETA = {"eam": 1 / KT_FE}
+ROWS = {"eam": (50, 500, 5000, 6144, 7168, 1 << 16)}  # 6,144 / 7,168: either side of EAM._FUSED_ROWS_MAX
+
+
 def start(kind, rows, dev):
     import torch
     g = torch.Generator().manual_seed(rows)
+    if kind == "eam":
+        import numpy as np
+        m = bench_eam()
+        c = np.arange(3)
+        corner = np.stack(np.meshgrid(c, c, c, indexing="ij"), -1).reshape(-1, 3).astype(np.float64)
+        lat = torch.as_tensor(np.concatenate((corner, corner + 0.5)) * m.A_FE, dtype=torch.float32)
+        x = lat + 0.08 * torch.randn(rows, m.N, 3, generator=g)
+        return x.to(dev), (KT_FE ** 0.5 * torch.randn(rows, m.N, 3, generator=g)).to(dev), 0.005
     lat = fcc32()
     if kind == "lj":
         x = lat + 0.03 * torch.randn(rows, 32, 3, generator=g)
@@ -105,11 +142,11 @@ def hmc_run_rows(a, dev):
     from normalizingflow_amd.hmc import HMC
     res = {"tool": "tools/bench_dynamics.py --hmc-run", "device": torch.cuda.get_device_name(0),
            "iters": a.iters, "windows": a.windows, "path_len": a.path_len, "epochs": a.epochs, "hmc_run": {}}
-    for kind in ("lj", "einstein"):
+    for kind in a.kinds:
         sim, _ = systems_pair(kind, dev)
         for chains in (1, 500):
             x, _, dt = start(kind, chains, dev)
-            run = HMC(sim, path_len=a.path_len, dt=dt)
+            run = HMC(sim, path_len=a.path_len, dt=dt, beta=BETA.get(kind, 1.0))
             torch.manual_seed(0)
             pa = run.hmc(8, x, one_launch=True, draw_bytes=0)[0]  # one epoch per launch: the default's draw order
             torch.manual_seed(0)
@@ -131,10 +168,14 @@ def main():
     ap.add_argument("--path-len", type=int, default=12)
     ap.add_argument("--hmc-run", action="store_true", help="time hmc(--epochs) in one launch against per epoch")
     ap.add_argument("--epochs", type=int, default=500)
+    ap.add_argument("--kind", choices=("eam",), default=None, help="eam: systems.EAM at the Fe shape alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.kinds = (a.kind,) if a.kind else ("lj", "einstein")
     if a.iters is None:
         a.iters = 3 if a.hmc_run else 10
+    if a.out is None and a.kind:
+        a.out = os.path.join(REPO, "profiles", "%s_dynamics_bench.json" % a.kind)
     if a.out is None:
         a.out = os.path.join(REPO, "profiles", "dynamics",
                              "bench_hmc_run.json" if a.hmc_run else "bench_dynamics.json")
@@ -142,17 +183,12 @@ def main():
     from normalizingflow_amd.hmc import HMC
     dev = torch.device("cuda", 0)
     if a.hmc_run:
-        res = hmc_run_rows(a, dev)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
-        print(json.dumps(res))
-        return 0
+        return save(a, hmc_run_rows(a, dev), "hmc_run")
     res = {"tool": "tools/bench_dynamics.py", "device": torch.cuda.get_device_name(0), "iters": a.iters,
            "windows": a.windows, "path_len": a.path_len, "trajectory": {}, "hmc_epoch": {}}
-    for kind in ("lj", "einstein"):
+    for kind in a.kinds:
         fused, slow = systems_pair(kind, dev)
-        for rows in (500, 5000):
+        for rows in ROWS.get(kind, (500, 5000)):
             x, v, dt = start(kind, rows, dev)
             xa, _ = fused.integration_step(a.path_len, dt, x, v)
             xb, _ = slow.integration_step(a.path_len, dt, x, v)
@@ -163,12 +199,24 @@ def main():
             print(kind, rows, json.dumps(r), flush=True)
         for chains in (1, 500):
             x, _, dt = start(kind, chains, dev)
-            runs = [HMC(s, path_len=a.path_len, dt=dt) for s in (fused, slow)]
+            runs = [HMC(s, path_len=a.path_len, dt=dt, beta=BETA.get(kind, 1.0)) for s in (fused, slow)]
             r = windows({"fused": lambda: runs[0].hmc(1, x, record=False),
                          "per_step": lambda: runs[1].hmc(1, x, record=False)}, a.iters, a.windows)
             r["note"] = "one hmc(1) call: the start potential, one epoch and the closing synchronisation"
             res["hmc_epoch"]["%s_chains%d" % (kind, chains)] = r
             print(kind, "hmc", chains, json.dumps(r), flush=True)
+    return save(a, res, "trajectory")
+
+
+def save(a, res, section):
+    """Write res; with --kind, into the kind's one file: the other invocation's
+    sections stay, each under the settings it was measured with."""
+    if a.kind:
+        res = {section + "_bench": {k: v for k, v in res.items() if not isinstance(v, dict)},
+               **{k: v for k, v in res.items() if isinstance(v, dict)}}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                res = {**json.load(f), **res}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         f.write(json.dumps(res, indent=1) + "\n")
