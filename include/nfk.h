@@ -916,6 +916,44 @@ int nfk_mbar(const float* u, int64_t ldu, int64_t N, int32_t K, const int64_t* n
              int64_t ldi, int64_t problems, const double* f0, int32_t max_iterations, double rtol,
              double* f, int32_t* iters, double* gram, nfk_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Metropolis chains over a batch of proposals (applications/src/utils.py:82-99),
+ * nfk_metropolize.hip: `chains` independent chains of N steps in one launch.
+ * Chain c reads e[c*lde + i] (reduced energies U/kT), lq[c*ldq + i] (log
+ * proposal densities; lq null: the reference's energy-only rule) and
+ * r[c*ldr + i] (uniforms in [0, 1)), all fp32.  Step i = 0 .. N-1 proposes
+ * sample i, in fp32 without contraction and in this order:
+ *   d = e_cur - e[i];  with lq: d = (d + lq_cur) - lq[i]
+ *   accept iff r[i] < expf(d)       (nfk_hmc_accept's test; a NaN rejects)
+ *   accepted: e_cur = e[i], lq_cur = lq[i], idx_cur = base + i
+ * Start: carry_in == 0 -- the chain starts at proposal 0 (e_cur = e[0],
+ * lq_cur = lq[0], idx_cur = base), so step 0 compares proposal 0 with itself,
+ * as the reference's loop does; carry_in != 0 -- it starts from e_cur[c],
+ * lq_cur[c] and idx_cur[c].  Whenever e_cur / lq_cur / idx_cur are given they
+ * receive the final state, so a chain is continued batch by batch with
+ * carry_in = 1 and `base` making the indices global.
+ * Outputs, each nullable: state[c*lds + i] (int32) = idx_cur after step i;
+ * accepted[c*lda + i] (uint8, 0 or 1); naccept[c] (int32) += the chain's
+ * acceptances, as nfk_*_hmc_run adds; the carried state.
+ * One wave per chain, four waves per workgroup, grid-stride over the chains.
+ * A wave takes 64 consecutive proposals, one per lane; the pending lanes test
+ * against the current state, a ballot finds the first that accepts, the state
+ * moves to its values and the lanes after it stay pending, until the ballot is
+ * empty: 1 + (acceptances in the block) rounds, each decision on the serial
+ * loop's operands, hence the serial loop's bits.  No LDS, no atomics; ordinary
+ * vector stores.  The arrays do not overlap.
+ * NFK_EINVAL, nothing launched: chains or N below zero; base below zero or
+ * base + N above INT32_MAX; and, with chains > 0 and N > 0, a null e or r;
+ * exactly one of e_cur / idx_cur; lq_cur without e_cur, or with e_cur exactly
+ * one of lq / lq_cur; carry_in without e_cur; with chains > 1 a row stride
+ * (lde, ldr, ldq with lq, lds with state, lda with accepted) below N.
+ * chains == 0 or N == 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------- */
+int nfk_metropolize(const float* e, int64_t lde, const float* lq, int64_t ldq, const float* r, int64_t ldr,
+                    int64_t chains, int64_t N, int32_t base, int32_t carry_in, float* e_cur, float* lq_cur,
+                    int32_t* idx_cur, int32_t* state, int64_t lds, uint8_t* accepted, int64_t lda,
+                    int32_t* naccept, nfk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -266,6 +266,11 @@ SIGNATURES = {
         P, I64, I64, P,                 # idx, ldi, problems, f0 (host double[K] or null)
         I32, F64,                       # max_iterations, rtol
         P, P, P, P]),                   # f, iters, gram, stream
+    "nfk_metropolize": (ctypes.c_int, [
+        P, I64, P, I64, P, I64,         # e, lde, lq, ldq, r, ldr
+        I64, I64, I32, I32,             # chains, N, base, carry_in
+        P, P, P,                        # e_cur, lq_cur, idx_cur
+        P, I64, P, I64, P, P]),         # state, lds, accepted, lda, naccept, stream
 }
 
 _lock = threading.Lock()

@@ -23,6 +23,10 @@ restated for the flow path.
   with its asymptotic error (mbar.py); Q never leaves its device.
 * ``fe_diff_no_training`` -- the prior-against-target driver of test.py:74-88
   over mbar.py's solver.
+* ``metropolize`` -- the Metropolis chain over a batch of frames of
+  utils.py:82-99, one energy call and one launch (reweight.py);
+  ``metropolized_samples`` -- flow samples, their energies and the independence
+  sampler over them, with acceptance rates and effective sample sizes.
 * ``collect_hmc_data`` / ``integrate_out_v`` / ``relaxation_step`` -- the
   dynamics of applications/src/dynamics.py over systems.py's own integrators
   (no LAMMPS), every trajectory of a call in one launch.
@@ -41,6 +45,7 @@ import yaml
 from . import bar as bar_
 from . import flows as F_
 from . import mbar as mbar_
+from . import reweight as reweight_
 from . import systems
 from .hmc import HMC
 from .models import NormalizingFlowModel
@@ -49,7 +54,7 @@ __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flo
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
            "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
            "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff",
-           "fe_diff_no_training"]
+           "fe_diff_no_training", "metropolize", "metropolized_samples"]
 
 
 class CfgNode(dict):
@@ -441,6 +446,74 @@ def fe_diff(cfg, model, potential, nsamples, relaxation=False, return_err=False,
     else:
         Q = q_matrix(cfg, model, potential, nsamples, batchsize=batchsize)
     return fe_estimates(cfg, Q, nboot=nboot if return_err else 0, generator=generator, emus=emus)
+
+
+def metropolize(cfg, potential, x, burnin=20, *, log_q=None, generator=None, return_chain=False):
+    """utils.py:82-99: the Metropolis chain whose proposal at step i is frame i
+    of ``x`` (N frames of ``nparticles * dim`` coordinates).  All N energies come
+    from one ``potential.potential`` call, the uniforms from one ``torch.rand(N,
+    generator=generator)`` on x's device, and the chain is one launch
+    (``reweight.metropolis_chain``); nothing is moved to the host.
+
+    Returns the reference's pair: ``x[index]`` ([M, nparticles, dim]), where
+    ``index[i]`` is true where step i accepted and ``i > burnin``, and the reduced
+    energies U/kT of every accepted step, burn-in included, as a tensor (the
+    reference returns a list).
+
+    With ``log_q=None`` the test is the reference's, ``r < exp(U_cur/kT -
+    U_i/kT)``, on the energy alone: it samples the target only if the frames
+    were proposed uniformly, which samples of a flow are not.  With ``log_q``,
+    the flow's log density of every frame ([N]), it is the independence sampler
+    ``r < exp((U_cur/kT + log q_cur) - (U_i/kT + log q_i))``, whose stationary
+    distribution is the target.
+
+    ``return_chain=True`` returns ``(x[state[burnin+1:]], e[state[burnin+1:]],
+    acceptance rate)`` instead: the chain's state after every step past the
+    burn-in, repeats included, its reduced energies, and naccept / N as a 0-d
+    tensor.  The shapes are fixed and nothing here synchronises (the potential's
+    own NaN check follows ``config.STRICT_CHECKS``), so the call can be captured
+    in a graph."""
+    d = cfg.dataset
+    frames = x.detach().reshape(-1, d.nparticles, d.dim)
+    e = (potential.potential(frames) / d.kT).detach().reshape(-1).to(frames.device)
+    N = e.numel()
+    r = torch.rand(N, generator=generator, device=frames.device).to(e.dtype)
+    lq = None if log_q is None else log_q.detach().reshape(-1).to(e.device)
+    state, accepted, naccept, _ = reweight_.metropolis_chain(e, r, lq)
+    if return_chain:
+        kept = state[burnin + 1:].long()
+        return frames[kept], e[kept], naccept.double() / max(N, 1)
+    index = accepted.clone()
+    index[:burnin + 1] = False
+    return frames[index], e[accepted]
+
+
+def metropolized_samples(cfg, model, potential, nsamples, batchsize=500, chains=1, burnin=0, generator=None):
+    """Samples of the target from the flow: ``chains * nsamples`` flow samples
+    with their log q (``generate_from_nf``; the product must be a multiple of
+    ``batchsize``), their energies in one ``potential.potential`` call, and
+    ``chains`` independence-sampler chains over ``nsamples`` proposals each in one
+    launch (the correct rule of ``metropolize``, uniforms from one ``torch.rand``
+    through ``generator``).  Returns ``(x_chain [chains, nsamples - burnin, W],
+    acceptance [chains], ess [chains])``: every chain's states from step
+    ``burnin`` on, its acceptance rate over all steps, and the Kish effective
+    sample size of its proposals' importance weights (``reweight.ess``), both
+    fp64.  The chain and the weights do not synchronise."""
+    d = cfg.dataset
+    total = chains * nsamples
+    if total < 1 or total % batchsize:
+        raise ValueError("chains * nsamples = %d must be a positive multiple of batchsize %d" % (total, batchsize))
+    with torch.no_grad():
+        x, log_q = generate_from_nf(model, total, batchsize=batchsize)
+    x, log_q = x.detach(), log_q.detach().reshape(chains, nsamples)
+    e = (potential.potential(x.reshape(-1, d.nparticles, d.dim)) / d.kT).detach().to(x.device)
+    e = e.reshape(chains, nsamples)
+    r = torch.rand(chains, nsamples, generator=generator, device=x.device).to(e.dtype)
+    state, _, naccept, _ = reweight_.metropolis_chain(e, r, log_q.to(e.dtype))
+    rows = x.reshape(chains, nsamples, -1)
+    kept = state[:, burnin:].long().unsqueeze(-1).expand(-1, -1, rows.shape[-1])
+    return (torch.gather(rows, 1, kept), naccept.double() / nsamples,
+            reweight_.ess(reweight_.log_weights(log_q, e)))
 
 
 def fe_diff_no_training(cfg, model, potential, nsamples):

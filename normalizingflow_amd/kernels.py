@@ -841,6 +841,50 @@ def mbar(u, n_k, f, iters, gram, *, idx=None, f0=None, max_iterations=1000, rtol
            float(rtol), f.data_ptr(), _vec(iters, P, "iters", torch.int32), gram.data_ptr(), _stream(dev))
 
 
+def _rows(t, C, N, name, dtype=F32):
+    """(ptr, row stride) of a [C, N] matrix of ``dtype`` with unit column stride; None -> (None, 0)."""
+    if t is None:
+        return None, 0
+    if t.dtype != dtype or t.dim() != 2 or t.shape != (C, N):
+        raise ValueError("%s must be a %s [%d, %d] matrix, got %s %s" % (name, dtype, C, N, t.dtype, tuple(t.shape)))
+    if N > 1 and t.stride(1) != 1:
+        raise ValueError("%s needs unit column stride" % name)
+    if C > 1 and t.stride(0) < N:
+        raise ValueError("%s rows overlap (row stride %d below %d)" % (name, t.stride(0), N))
+    return t.data_ptr(), (t.stride(0) if C > 1 else max(N, 1))
+
+
+def metropolize(e, r, *, lq=None, state=None, accepted=None, naccept=None, e_cur=None, lq_cur=None, idx_cur=None,
+                carry_in=False, base=0):
+    """nfk_metropolize: e.shape[0] independent Metropolis chains over the
+    e.shape[1] proposals of their rows in one launch.  e, r and lq (optional)
+    are fp32 [C, N] with unit column stride; state [C, N] int32, accepted [C, N]
+    uint8 and naccept [C] int32 (added to) are optional outputs; e_cur, lq_cur
+    [C] fp32 and idx_cur [C] int32 receive the final state (lq_cur exactly with
+    lq) and, with ``carry_in``, hold the start."""
+    dev = _require_hip(e, r, lq, state, accepted, naccept, e_cur, lq_cur, idx_cur)
+    if e.dim() != 2:
+        raise ValueError("e must be 2-D, got shape %s" % (tuple(e.shape),))
+    C, N = e.shape
+    base = int(base)
+    if base < 0 or base + N > 2 ** 31 - 1:
+        raise ValueError("base must be >= 0 and base + N fit int32 (base %d, N %d)" % (base, N))
+    if (e_cur is None) != (idx_cur is None):
+        raise ValueError("e_cur and idx_cur come together")
+    if (lq_cur is not None) != (lq is not None and e_cur is not None):
+        raise ValueError("lq and lq_cur come together")
+    if carry_in and e_cur is None:
+        raise ValueError("carry_in needs e_cur and idx_cur")
+    ep, lde = _rows(e, C, N, "e")
+    qp, ldq = _rows(lq, C, N, "lq")
+    rp, ldr = _rows(r, C, N, "r")
+    sp, lds = _rows(state, C, N, "state", torch.int32)
+    ap, lda = _rows(accepted, C, N, "accepted", torch.uint8)
+    _timed("nfk_metropolize", dev, "nfk_metropolize", ep, lde, qp, ldq, rp, ldr, C, N, base, 1 if carry_in else 0,
+           _vec(e_cur, C, "e_cur"), _vec(lq_cur, C, "lq_cur"), _vec(idx_cur, C, "idx_cur", torch.int32),
+           sp, lds, ap, lda, _vec(naccept, C, "naccept", torch.int32), _stream(dev))
+
+
 def trig_features(x, feat, B):
     dev = _require_hip(x, feat)
     n_rows, n = x.shape

@@ -4,6 +4,7 @@ on one GPU against the two host forms it replaces.
 
     python tools/bench_fe.py [--out profiles/fe/bench_fe.json]
     python tools/bench_fe.py --mbar [--out profiles/fe/bench_mbar.json]
+    python tools/bench_fe.py --metropolize [--out profiles/metropolize_bench.json]
 
 Three forms of the same work alternate inside one process, window by window:
 
@@ -27,6 +28,17 @@ mbar.py) instead, by the same method and in the same three forms: one solve and
 a 200-replica stratified bootstrap of 500 + 500 samples at K = 2 (the work
 values above as two states) and of 4,096 samples of K = 8 states (512 each,
 harmonic wells with offsets of 40 per state: N K is the kernel's LDS cap).
+
+``--metropolize`` times ``reweight.metropolis_chain`` alone (nfk_metropolize.hip)
+on synthetic energies whose acceptance rate is about 0.05, 0.5 and 1.0 (a
+strictly decreasing e: the most rounds per block the kernel can take), at
+(chains, proposals) = (1, 2000), (10, 2000), (200, 2000) and (1, 2^20), in three
+forms: the kernel; the torch restatement on the same GPU (``use_kernels =
+False``); and the reference's per-frame loop on CPU tensors with the energies
+precomputed.  The last two are serial in the steps and are timed on at most
+2^14 steps (the loop on one chain); the result file holds those times and
+their linear scaling to the whole shape, named as such.  Default output:
+profiles/metropolize_bench.json.
 """
 from __future__ import annotations
 
@@ -145,8 +157,11 @@ def main():
     ap.add_argument("--budget", type=float, default=0.2, help="seconds of calls per variant and window")
     ap.add_argument("--nboot", type=int, default=200)
     ap.add_argument("--mbar", action="store_true", help="time the multistate solver instead")
+    ap.add_argument("--metropolize", action="store_true", help="time the Metropolis chain instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None and a.metropolize:
+        a.out = os.path.join(REPO, "profiles", "metropolize_bench.json")
     if a.out is None:
         a.out = os.path.join(REPO, "profiles", "fe", "bench_mbar.json" if a.mbar else "bench_fe.json")
     import numpy as np
@@ -156,6 +171,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_fe.py needs a HIP device")
     dev = torch.device("cuda", 0)
+    if a.metropolize:
+        return main_metropolize(a, dev)
 
     def torch_path(fn):
         def run():
@@ -309,6 +326,78 @@ def main_mbar(a, dev, work):
         r["nboot"], r["K"], r["N"], r["form"] = a.nboot, K, N, form
         res["bootstrap"][name] = r
         print("bootstrap", name, json.dumps(r), flush=True)
+
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+    return 0
+
+
+def reference_chain(e, r):
+    """The per-frame loop of applications/src/utils.py:86-99 on CPU tensors, with
+    the energies precomputed (its energy call per frame is not part of this
+    measurement): one 0-d tensor operation and one host comparison per step."""
+    import torch
+    energy, n = e[0], 0
+    for i in range(len(e)):
+        if r[i] < torch.exp(energy - e[i]):
+            energy = e[i]
+            n += 1
+    return n
+
+
+def main_metropolize(a, dev):
+    import torch
+    from normalizingflow_amd import reweight as R
+
+    PREFIX = 1 << 14  # the torch path and the reference loop are timed on at most this many steps
+
+    def torch_path(fn):
+        def run():
+            R.use_kernels = False
+            try:
+                return fn()
+            finally:
+                R.use_kernels = True
+        return run
+
+    def energies(C, N, rate, seed):
+        """fp32 energies whose energy-only chain accepts at about ``rate``:
+        i.i.d. N(0, s^2) accepts at 2 Phi(-s / sqrt 2) once stationary (s 0.954:
+        0.5, s 2.772: 0.05); strictly decreasing accepts every step."""
+        g = torch.Generator().manual_seed(seed)
+        if rate == 1.0:
+            e = -(torch.arange(N, dtype=torch.float32) / 64.0).expand(C, N).contiguous()
+        else:
+            e = {0.5: 0.954, 0.05: 2.772}[rate] * torch.randn(C, N, generator=g)
+        return e, torch.rand(C, N, generator=g)
+
+    res = {"tool": "tools/bench_fe.py --metropolize", "device": torch.cuda.get_device_name(0), "windows": a.windows,
+           "budget_s": a.budget, "prefix_steps": PREFIX, "shapes": {}}
+    for C, N in ((1, 2000), (10, 2000), (200, 2000), (1, 1 << 20)):
+        for rate in (0.05, 0.5, 1.0):
+            e, r = energies(C, N, rate, C + N)
+            de, dr = e.to(dev), r.to(dev)
+            n = min(N, PREFIX)
+            pe, pr = de[:, :n].contiguous(), dr[:, :n].contiguous()
+            ce, cr = e[0, :n].contiguous(), r[0, :n].contiguous()
+            state, accepted, naccept, _ = R.metropolis_chain(de, dr)
+            t = timed({"kernel": lambda: R.metropolis_chain(de, dr),
+                       "torch": torch_path(lambda: R.metropolis_chain(pe, pr)),
+                       "reference_loop": lambda: reference_chain(ce, cr)}, a.windows, a.budget)
+            row = {"C": C, "N": N, "target_rate": rate, "acceptance": round(float(naccept.double().mean()) / N, 4),
+                   "kernel": t["kernel"], "kernel_device_ms": device_ms(lambda: R.metropolis_chain(de, dr)),
+                   # the torch path on the first `steps` steps of all C chains; the reference loop on the
+                   # first `steps` steps of ONE chain.  Both are serial in the steps, the loop in the chains
+                   # too: the *_scaled_ms entries are the medians times N / steps (and times C)
+                   "torch": dict(t["torch"], steps=n), "reference_loop": dict(t["reference_loop"], steps=n, chains=1)}
+            row["torch_scaled_ms"] = round(t["torch"]["median_ms"] * N / n, 3)
+            row["reference_loop_scaled_ms"] = round(t["reference_loop"]["median_ms"] * N / n * C, 3)
+            row["kernel_over_torch"] = round(row["torch_scaled_ms"] / t["kernel"]["median_ms"], 1)
+            row["kernel_over_reference_loop"] = round(row["reference_loop_scaled_ms"] / t["kernel"]["median_ms"], 1)
+            res["shapes"]["c%d_n%d_rate%g" % (C, N, rate)] = row
+            print("metropolize", C, N, rate, json.dumps(row), flush=True)
 
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
