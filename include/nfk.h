@@ -954,6 +954,44 @@ int nfk_metropolize(const float* e, int64_t lde, const float* lq, int64_t ldq, c
                     int32_t* idx_cur, int32_t* state, int64_t lds, uint8_t* accepted, int64_t lda,
                     int32_t* naccept, nfk_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Weighted pair-distance histogram of a batch of configurations, the counts
+ * behind the radial distribution function g(r) (nfk_pair_hist.hip; the
+ * reference has no counterpart, its drivers stop at plot_Q).
+ * x holds `batch` rows of n * dim fp32 (row stride ldx); w (nullable: 1 for every
+ * row) one fp64 weight per row.  For every row b and every pair i < j, in fp32:
+ *   d = x_i - x_j per component; with a box (lx, ly and, for dim 3, lz > 0)
+ *   the minimum image d - L * rint(d * (1 / L)) per component, so positions
+ *   need not lie in the box or within one box length of each other; with box
+ *   lengths 0 no wrap (lz is ignored for dim 2);
+ *   r = sqrt(sum d^2), k = (int)(r * (float)(nbins / r_max));
+ *   the pair counts in bin k iff r < (float)r_max and k < nbins.
+ * Pairs at or beyond r_max land in no bin, and so do pairs whose r is NaN or
+ * infinite (the compare is false; there is no status word).
+ *   hist[k] = sum_b w_b * count_b[k]      (fp64 [nbins])
+ * A row's counts are uint32 in LDS (integer adds: any order); w_b multiplies
+ * them in fp64 when the row is folded into its wave's accumulator.  Workgroup g
+ * of nfk_pair_hist_parts(batch) takes, with its four waves v, the rows
+ * (t * parts + g) * 4 + v, t = 0, 1, ..; it adds its accumulators in wave order
+ * into partial g of `workspace` (fp64, nfk_pair_hist_workspace_elems(batch,
+ * nbins) = parts * nbins elements, caller-owned), and a second launch on the
+ * same stream adds the partials in index order into hist.  No floating-point
+ * atomics and no host sync: capturable on one stream; for a given input and
+ * batch, hist is bitwise the same run to run, and with unit weights every entry
+ * is an exact integer while it stays below 2^53.
+ * NFK_EINVAL, nothing launched: !nfk_pair_hist_supported(n, dim, nbins)
+ * (1 <= n <= 256, dim 2 or 3, 1 <= nbins <= 1024); batch < 0; null hist; with
+ * batch > 0 a null x or workspace; r_max not a number > 0; a negative or
+ * non-finite box length, or some positive and some zero; a box with r_max >
+ * min(L) / 2; ldx < n * dim with batch > 1.  batch == 0 writes zeros to hist.
+ * ------------------------------------------------------------------------- */
+int nfk_pair_hist_supported(int32_t n, int32_t dim, int32_t nbins); /* host-only */
+int64_t nfk_pair_hist_parts(int64_t batch);                         /* host-only: partials, by batch alone */
+int64_t nfk_pair_hist_workspace_elems(int64_t batch, int32_t nbins); /* host-only: fp64 elements */
+int nfk_pair_hist(const float* x, int64_t ldx, const double* w, int64_t batch, int32_t n, int32_t dim,
+                  double lx, double ly, double lz, double r_max, int32_t nbins, double* hist,
+                  double* workspace, nfk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

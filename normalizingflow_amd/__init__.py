@@ -7,6 +7,8 @@ Public surface mirrors the reference (re-exported as the ``nf`` package):
     from nf.utils import unconstrained_RQS, RQS, searchsorted
 The applications' priors and targets (applications/src/systems.py):
     from normalizingflow_amd.systems import EinsteinCrystal, GaussianMixture, LJ
+Structure of a batch of configurations (no reference counterpart):
+    from normalizingflow_amd.observables import pair_histogram, rdf, coordination
 """
 from . import config  # noqa: F401
 from . import systems  # noqa: F401

@@ -271,6 +271,13 @@ SIGNATURES = {
         I64, I64, I32, I32,             # chains, N, base, carry_in
         P, P, P,                        # e_cur, lq_cur, idx_cur
         P, I64, P, I64, P, P]),         # state, lds, accepted, lda, naccept, stream
+    "nfk_pair_hist_supported": (ctypes.c_int, [I32, I32, I32]),
+    "nfk_pair_hist_parts": (ctypes.c_int64, [I64]),
+    "nfk_pair_hist_workspace_elems": (ctypes.c_int64, [I64, I32]),
+    "nfk_pair_hist": (ctypes.c_int, [
+        P, I64, P, I64, I32, I32,       # x, ldx, w, batch, n, dim
+        F64, F64, F64, F64, I32,        # lx, ly, lz, r_max, nbins
+        P, P, P]),                      # hist, workspace, stream
 }
 
 _lock = threading.Lock()

@@ -27,6 +27,9 @@ restated for the flow path.
   utils.py:82-99, one energy call and one launch (reweight.py);
   ``metropolized_samples`` -- flow samples, their energies and the independence
   sampler over them, with acceptance rates and effective sample sizes.
+* ``structure`` -- the radial distribution functions of the flow's samples, of
+  the same samples under their importance weights and of the target's samples
+  on one grid, with the weights' effective sample size (observables.py).
 * ``collect_hmc_data`` / ``integrate_out_v`` / ``relaxation_step`` -- the
   dynamics of applications/src/dynamics.py over systems.py's own integrators
   (no LAMMPS), every trajectory of a call in one launch.
@@ -45,6 +48,7 @@ import yaml
 from . import bar as bar_
 from . import flows as F_
 from . import mbar as mbar_
+from . import observables as observables_
 from . import reweight as reweight_
 from . import systems
 from .hmc import HMC
@@ -54,7 +58,7 @@ __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flo
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
            "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
            "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff",
-           "fe_diff_no_training", "metropolize", "metropolized_samples"]
+           "fe_diff_no_training", "metropolize", "metropolized_samples", "structure"]
 
 
 class CfgNode(dict):
@@ -514,6 +518,41 @@ def metropolized_samples(cfg, model, potential, nsamples, batchsize=500, chains=
     kept = state[:, burnin:].long().unsqueeze(-1).expand(-1, -1, rows.shape[-1])
     return (torch.gather(rows, 1, kept), naccept.double() / nsamples,
             reweight_.ess(reweight_.log_weights(log_q, e)))
+
+
+def structure(cfg, model, potential, nsamples, batchsize=500, nbins=100, r_max=None):
+    """The structure of the flow's samples against the target's, as radial
+    distribution functions on one grid (``observables.rdf``): ``nsamples`` flow
+    samples with their log q (``generate_from_nf``, as ``q_matrix`` draws them)
+    and their energies over kT in one ``potential.potential`` call, and
+    ``potential.sample(nsamples)``.  Returns a dict:
+
+        r             bin centres [nbins]
+        g_flow        g(r) of the flow's samples as drawn
+        g_reweighted  g(r) of the same samples under their importance weights
+                      (``reweight.log_weights``, self-normalised)
+        g_target      g(r) of the target's samples
+        ess           the Kish effective sample size of those weights (0-d)
+
+    all fp64 on the model's device.  The box is ``potential.boxlength`` (a scalar
+    or one length per dimension), else ``cfg.dataset.boxlength``; ``r_max=None``
+    is half its shortest length.  Nothing leaves the device and nothing is
+    written."""
+    d = cfg.dataset
+    box = getattr(potential, "boxlength", None)
+    if box is None:
+        box = d.boxlength
+    with torch.no_grad():
+        x, log_q = generate_from_nf(model, nsamples, batchsize=batchsize)
+    x, log_q = x.detach().reshape(-1, d.nparticles, d.dim), log_q.detach()
+    e = (potential.potential(x) / d.kT).detach().reshape(-1).to(x.device)
+    logw = reweight_.log_weights(log_q.to(e.dtype), e)
+    target = potential.sample(nsamples)
+    target = target.reshape(len(target), d.nparticles, d.dim).to(x.device)
+    r, g_flow = observables_.rdf(x, box, r_max=r_max, nbins=nbins)
+    _, g_rew = observables_.rdf(x, box, r_max=r_max, nbins=nbins, log_weights=logw)
+    _, g_target = observables_.rdf(target, box, r_max=r_max, nbins=nbins)
+    return {"r": r, "g_flow": g_flow, "g_reweighted": g_rew, "g_target": g_target, "ess": reweight_.ess(logw)}
 
 
 def fe_diff_no_training(cfg, model, potential, nsamples):

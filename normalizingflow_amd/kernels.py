@@ -885,6 +885,43 @@ def metropolize(e, r, *, lq=None, state=None, accepted=None, naccept=None, e_cur
            sp, lds, ap, lda, _vec(naccept, C, "naccept", torch.int32), _stream(dev))
 
 
+def pair_hist_supported(n, dim, nbins):
+    """True for the shapes nfk_pair_hist is built for (n 1..256, dim 2 or 3, nbins 1..1024)."""
+    return bool(_lib.load().nfk_pair_hist_supported(int(n), int(dim), int(nbins)))
+
+
+def pair_hist_parts(batch):
+    """The number of partial histograms nfk_pair_hist sums for ``batch`` rows."""
+    return int(_lib.load().nfk_pair_hist_parts(int(batch)))
+
+
+def pair_hist_workspace_elems(batch, nbins):
+    """fp64 elements of workspace nfk_pair_hist needs."""
+    return int(_lib.load().nfk_pair_hist_workspace_elems(int(batch), int(nbins)))
+
+
+def pair_hist(x, hist, workspace, *, n, dim, box, r_max, weights=None):
+    """nfk_pair_hist.  x: [B, n*dim] fp32 rows with unit column stride; ``box`` the
+    three box lengths (zeros: no box); ``weights`` None or fp64 [B]; hist fp64
+    [nbins]; workspace fp64 with at least pair_hist_workspace_elems(B, nbins)
+    elements (None only for B == 0)."""
+    dev = _require_hip(x, hist, workspace, weights)
+    B = x.shape[0]
+    xp, ldx = _mat(x, "x")
+    if x.shape[1] != n * dim:
+        raise ValueError("x must be [B, %d], got %s" % (n * dim, tuple(x.shape)))
+    if hist.dtype != torch.float64 or hist.dim() != 1 or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous float64 vector")
+    nbins = hist.numel()
+    need = pair_hist_workspace_elems(B, nbins) if pair_hist_supported(n, dim, nbins) else 0
+    if workspace is not None and (workspace.dtype != torch.float64 or not workspace.is_contiguous()
+                                  or workspace.numel() < need):
+        raise ValueError("workspace must be contiguous float64 with at least %d elements" % need)
+    lx, ly, lz = (float(v) for v in box)
+    _timed("nfk_pair_hist", dev, "nfk_pair_hist", xp, ldx, _vec(weights, B, "weights", torch.float64), B, n, dim,
+           lx, ly, lz, float(r_max), nbins, hist.data_ptr(), _ptr(workspace), _stream(dev))
+
+
 def trig_features(x, feat, B):
     dev = _require_hip(x, feat)
     n_rows, n = x.shape
