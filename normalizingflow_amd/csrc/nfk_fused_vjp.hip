@@ -66,14 +66,24 @@ __device__ __forceinline__ void vjp_parts(const h8 (&bh)[KBH], const h8 (&bl)[KB
 
 // hidden activations (scaled tanh in h[][], see act_operands) -> row b of out:
 // tile t < 2 KBH holds features 32 (t >> 1) + 8 q + 4 (t & 1) + r; the tail tile
-// features 32 KBH + r (r < H - 32 KBH, from lane group 0); 1 at column H
+// features 32 KBH + r (r < H - 32 KBH, from lane group 0); 1 at column H.
+// A width rounded up to the k-block (no tail, H < 32 KBH: make_layout) has
+// zero-padded features in its last k-block; the row holds ldh >= H + 1 floats
+// only, so that block's quads store their columns below H and nothing else.
 template <int KBH, bool T1, int HT>
 __device__ __forceinline__ void store_act(const f32x4 (&h)[HT], float* row, int q, int H) {
     constexpr float un = 1.0f / kActScale;
 #pragma unroll
-    for (int t = 0; t < 2 * KBH; ++t)
-        *reinterpret_cast<float4*>(row + 32 * (t >> 1) + 8 * q + 4 * (t & 1)) =
-            make_float4(h[t][0] * un, h[t][1] * un, h[t][2] * un, h[t][3] * un);
+    for (int t = 0; t < 2 * KBH; ++t) {
+        const int c = 32 * (t >> 1) + 8 * q + 4 * (t & 1);
+        if (T1 || t < 2 * (KBH - 1) || c + 4 <= H) {
+            *reinterpret_cast<float4*>(row + c) = make_float4(h[t][0] * un, h[t][1] * un, h[t][2] * un, h[t][3] * un);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (c + r < H) row[c + r] = h[t][r] * un;
+        }
+    }
     if constexpr (T1) {
         if (q == 0)
 #pragma unroll

@@ -20,7 +20,15 @@ pytestmark = pytest.mark.gpu
 
 # (size, dim, K, hidden, mask): c3 (KBH 3 + tail, K 8), KBH 3 without a tail,
 # KBH 2 with K 4, KBH 1 + tail with a ragged last chunk (n_up 12)
-SHAPES = [(32, 2, 8, 100, [0]), (32, 2, 8, 96, [1]), (16, 2, 4, 64, [1]), (12, 2, 8, 33, [0])]
+SHAPES = [(32, 2, 8, 100, [0]), (32, 2, 8, 96, [1]), (16, 2, 4, 64, [1]), (12, 2, 8, 33, [0]),
+          # the other four compiled (KBH, tail, K) instances: (1,1,4), (2,0,8), (3,0,4), (3,1,4)
+          (8, 2, 4, 33, [0]), (16, 2, 8, 64, [0]), (16, 2, 4, 96, [0]), (16, 2, 4, 100, [0]),
+          # hidden widths rounded up to the k-block (KBH 2 and 3 without a tail): the
+          # layer allocates h1 / h2 rows of hidden + 1 floats, so these cover the
+          # weight gradients end to end (store_act at padded widths)
+          (16, 2, 8, 50, [1]), (16, 2, 8, 80, [0]),
+          # dim 3, a non-adjacent lower / upper column map
+          (8, 3, 8, 100, [1])]
 
 
 def _grads(layer, x, w, v, inverse):
