@@ -30,7 +30,9 @@
 // and a chunk of KC k-blocks: the chunk's input fragments (MT sample tiles)
 // are copied into LDS once (LDS-DMA) and shared by the 4 waves; each wave
 // streams its NTW tiles' weights from HBM straight into registers, kWlPF
-// k-blocks ahead, and writes fp32 partial sums [group][split][row][feature].
+// k-blocks ahead, and writes fp32 partial sums [group][split][row][feature]
+// (each the difference of two accumulators, the chunk's even k-blocks and its
+// negated odd ones: the MFMA unit's rounding offset cancels, see k_wl_gemm).
 // The split count is chosen so the grid covers every CU (>= 256 workgroups)
 // with as few partial sums as that allows; they are summed in split order by
 // the next stage (deterministic, bitwise reproducible).
@@ -167,11 +169,24 @@ __global__ __launch_bounds__(64 * NW, 1) void k_wl_gemm(WlGemm a) {
 #pragma unroll
     for (int j = 0; j < kWlPF; ++j) issue(j, w[j]);
 
-    f32x4 acc[NTW][MT];
+    // two accumulators per tile: the even k-blocks of the chunk add to the
+    // first, the odd ones with their weights negated to the second, and the
+    // partial sum is their difference.  The MFMA unit's sum of 32 products and
+    // the accumulator is not rounded symmetrically (measured against the exact
+    // products of the fragments read: -7 units of the scaled accumulator per
+    // output over L3's contraction, 2e-10 in s, whatever the sign of the sum);
+    // the same offset in both halves cancels, where in one accumulator it adds
+    // up over the k-blocks and then over the columns of log|det| = sum s.  (A
+    // chunk of one k-block, KC = 1, has no odd half and keeps its offset: wl_plan
+    // gives such chunks only to small stages, KB ceil(N / 128) <= 128.)
+    static_assert(PF % 2 == 0, "the k-block's parity is its ring position's");
+    f32x4 acc[2][NTW][MT];
 #pragma unroll
-    for (int t = 0; t < NTW; ++t)
+    for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int s = 0; s < MT; ++s) acc[t][s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+            for (int s = 0; s < MT; ++s) acc[e][t][s] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const int nkr = (nkc + kWlPF - 1) / kWlPF * kWlPF;
     for (int k0 = 0; k0 < nkr; k0 += kWlPF) {
 #pragma unroll
@@ -191,12 +206,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_wl_gemm(WlGemm a) {
             }
 #pragma unroll
             for (int t = 0; t < NTW; ++t) {
-                const h8 ah = __builtin_bit_cast(h8, w[j][t][0]), al = __builtin_bit_cast(h8, w[j][t][1]);
+                const int odd = j & 1;  // (kk's parity: k0 is a multiple of the even kWlPF; a constant once unrolled)
+                const h8 wh = __builtin_bit_cast(h8, w[j][t][0]), wl = __builtin_bit_cast(h8, w[j][t][1]);
+                const h8 ah = odd ? -wh : wh, al = odd ? -wl : wl;
 #pragma unroll
                 for (int s = 0; s < MT; ++s) {
-                    acc[t][s] = mfma16(al, xh[s], acc[t][s]);
-                    acc[t][s] = mfma16(ah, xl[s], acc[t][s]);
-                    acc[t][s] = mfma16(ah, xh[s], acc[t][s]);
+                    acc[odd][t][s] = mfma16(al, xh[s], acc[odd][t][s]);
+                    acc[odd][t][s] = mfma16(ah, xl[s], acc[odd][t][s]);
+                    acc[odd][t][s] = mfma16(ah, xh[s], acc[odd][t][s]);
                 }
             }
             // the slot refilled below was read one step ago: every wave has
@@ -222,7 +239,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_wl_gemm(WlGemm a) {
             const int m = 16 * s + n;
             if (m < a.M)
                 *reinterpret_cast<float4*>(P + (int64_t)m * a.N + f0) =
-                    make_float4(acc[t][s][0], acc[t][s][1], acc[t][s][2], acc[t][s][3]);
+                    make_float4(acc[0][t][s][0] - acc[1][t][s][0], acc[0][t][s][1] - acc[1][t][s][1],
+                                acc[0][t][s][2] - acc[1][t][s][2], acc[0][t][s][3] - acc[1][t][s][3]);
         }
     }
 }
@@ -499,9 +517,13 @@ __global__ __launch_bounds__(kRowThreads) void k_wl_rows(WlRows a) {
                 s = s * us + a.bias[0][c];
                 t = t * ut + a.bias[1][c];
                 const float x = xr[c];
-                // flows.py:56, 59 (t + x exp(s)) and 69, 72 ((x - t) exp(-s)),
-                // each operation rounded (no contraction: -ffp-contract=off)
-                const float o = a.inverse ? (x - t) * expf(-s) : t + x * expf(s);
+                // flows.py:56, 59 (t + x exp(s)) and 69, 72 ((x - t) exp(-s)) in
+                // double, rounded once: expf's own ulp times |x exp(s)|, on top
+                // of the product's and the sum's roundings, was 1.5 ulp of the
+                // largest outputs (3x the fp32 reference's error at half 4);
+                // one exp per output is nothing beside the weight stream
+                const double es = exp(a.inverse ? -(double)s : (double)s);
+                const float o = (float)(a.inverse ? ((double)x - (double)t) * es : (double)t + (double)x * es);
                 orow[c] = o;
                 lsum += s;
                 if (a.frag != nullptr) rowv[c] = o;

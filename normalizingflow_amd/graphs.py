@@ -36,7 +36,7 @@ from . import flows as _flows
 from .flows import check_status, flush_status_checks
 
 
-_CACHE_ATTRS = ("_pack_cache", "_vjp_cache", "_chain_cache", "_lp_plan_cache")
+_CACHE_ATTRS = ("_pack_cache", "_vjp_cache", "_chain_cache", "_lp_plan_cache", "_wide_cache")
 
 
 def _cache_refs(model):

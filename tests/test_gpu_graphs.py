@@ -133,6 +133,36 @@ def test_graphed_keeps_captured_packs_alive(hip_device):
     flush_status_checks()
 
 
+def test_graphed_keeps_captured_wide_rnvp_packs_alive(hip_device):
+    """The RealNVP twin of the test above: one weight-stream layer running
+    alone (nfk_wide_rnvp; too wide for the fused kernel, and a run of one is
+    no chain, so only the layer's _wide_cache holds its packs).  The graph
+    pins them: after a write through ``p.data``, invalidate_caches() and an
+    eager call that packs the new weights, the replay still reads its
+    capture's packs."""
+    torch.manual_seed(4321)
+    flows = [nff.RealNVP(200, hidden_dim=1000)]
+    prior = torch.distributions.MultivariateNormal(torch.zeros(200), torch.eye(200))
+    model = _to(nfm.NormalizingFlowModel(prior, flows), 200, hip_device)
+    x = 0.5 * torch.randn(40, 200, generator=torch.Generator(device=hip_device).manual_seed(5), device=hip_device)
+    assert model.flows[0]._fused_pack(hip_device) is None
+    assert model.flows[0]._wide_pack(hip_device, 40) is not None
+    gl = GraphedLogProb(model, x)
+    before = gl().clone()
+    model.flows[0].s1.network[0].weight.data.mul_(0.5)
+    model.invalidate_caches()
+    eager = model.log_prob(x)
+    assert not torch.equal(eager, before)
+    # churn the allocator: the freed blocks of unpinned packs would be reused here
+    junk = [torch.full((1 << 18,), float("nan"), device=hip_device) for _ in range(64)]
+    torch.cuda.synchronize()
+    assert not gl.stale()
+    assert torch.equal(gl().clone(), before)
+    del junk
+    assert torch.equal(gl.recapture()().clone(), eager)
+    flush_status_checks()
+
+
 def test_graphed_raises_reference_error_after_replay(hip_device):
     model = _nsf_model(hip_device, n_layers=2)
     x = torch.randn(256, 64, device=hip_device)
