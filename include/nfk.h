@@ -837,6 +837,91 @@ int nfk_eam_hmc_run(float* x_cur, int64_t ldx, float* u_cur, int32_t* naccept, c
                     double ly, double lz, double rc, nfk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Device random numbers, nfk_rng.h / nfk_langevin.hip: Philox4x32-10 with the
+ * Random123 constants (multipliers 0xD2511F53, 0xCD9E8D57; Weyl increments
+ * 0x9E3779B9, 0xBB67AE85; 10 rounds).  A call is addressed by
+ *   counter = (step_lo, step_hi, particle, row),  key = (seed_lo, seed_hi | tag << 31)
+ * with `step` the absolute 64-bit step index, row = (uint32)(row_base + b),
+ * 0 <= seed < 2^63 and tag 0 (thermostat noise) or 1 (initial velocities): a
+ * value never depends on the launch geometry.  The four words w of a call give
+ * four normals by two Box-Muller pairs, u = ((w >> 8) + 0.5f) * 2^-24 in fp32,
+ * r = sqrtf(-2 logf(u_a)), (z_a, z_b) = r * (cospif, sinpif)(2 u_b) for
+ * (a, b) = (0, 1) and (2, 3), accurate functions; |z| <= 5.89.  Component d of
+ * particle p is normal d of its call (dim <= 4).  zero_mean subtracts from each
+ * normal its dimension's mean over the row's n particles, summed as the row
+ * kernels do: a row on lanes_for(n) = next_pow2(n) <= 64 lanes, each lane its
+ * own particles c0 + q lanes in ascending order, the fixed butterfly over the
+ * lanes, then / (float)n.
+ * nfk_philox_fill writes, for rows b < rows and particles p < n, the raw words
+ * as int32 [rows, n, 4] (normals == 0) or the normals as fp32 [rows, n, dim]
+ * (normals != 0), dense.  NFK_EINVAL, nothing launched: n outside 1..2^24, dim
+ * outside 1..4 with normals, tag outside {0, 1}, zero_mean without normals,
+ * seed or step below zero (a seed of 2^63 or more), rows < 0, row_base < 0 or
+ * row_base + rows above 2^32, a null `out` with rows > 0.
+ * ------------------------------------------------------------------------- */
+int nfk_philox_fill(void* out, int32_t normals, int64_t rows, int32_t n, int32_t dim, int64_t step,
+                    int64_t row_base, int64_t seed, int32_t tag, int32_t zero_mean, nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Langevin (NVT) dynamics, nfk_langevin.hip: `nsteps` BAOAB steps of a batch of
+ * independent trajectories in ONE launch, the noise generated in the kernel.
+ * x_in, v_in, x_out, v_out, pot_out, batch and the system arguments are those
+ * of the system's nfk_*_trajectory (x_out may be x_in, v_out may be v_in), and
+ * so are the mappings, the LDS arrangement, the forces and the closing
+ * potential (nfk_systems_dev.h) and the supported shapes; the Einstein crystal
+ * additionally needs dim <= 4 (a lane holds component c % dim of atom c / dim).
+ * With F = force(x_in), per step k < nsteps, in fp32 without contraction and in
+ * this order:
+ *   v = v + hb*F;  x = x + hd*v;  v = c1*v + c2*xi;  x = x + hd*v;
+ *   F = force(x);  v = v + hb*F
+ * xi = the tag-0 normal of (seed, step0 + k, particle, row_base + b, component)
+ * above, less the row mean with zero_mean.  The host computes in double and
+ * rounds to fp32 once: hb = 0.5 dt / mass, hd = 0.5 dt, c1 = exp(-gamma dt),
+ * c2 = sqrt(kT / mass * (1 - c1^2)).  Positions are not wrapped.  Since the
+ * noise is keyed by the absolute step and F is recomputed from x, a run cut
+ * into several calls (step0 advanced, x and v carried) or into row blocks
+ * (row_base advanced) equals the single call bit for bit, and a call equals,
+ * bit for bit in x, v and the potentials, the chain of nfk_philox_fill, force
+ * kernels and elementwise fp32 ops it replaces.
+ * Records: with record_every > 0 and pos_rec / pot_rec given (both or neither),
+ * after every step with (step0 + k + 1) % record_every == 0 the positions go to
+ * pos_rec[f, b, :W] and their potential to pot_rec[f, b], dense, f = (step0 + k
+ * + 1) / record_every - 1 - step0 / record_every: (step0 + nsteps) /
+ * record_every - step0 / record_every frames.  The potential is evaluated only
+ * there and at the end.  Plain vector stores, no atomics, nothing between
+ * workgroups.  The records overlap nothing else.
+ * NFK_EINVAL, nothing launched: what the system's nfk_*_trajectory refuses about
+ * its arguments; nsteps, step0 or record_every below zero; exactly one of
+ * pos_rec / pot_rec; a seed outside [0, 2^63); row_base < 0 or row_base + batch
+ * above 2^32; an unsupported shape.
+ * ------------------------------------------------------------------------- */
+int nfk_einstein_langevin(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out,
+                          int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out, int64_t batch,
+                          int32_t nsteps, int64_t step0, int64_t row_base, int64_t seed, int32_t zero_mean,
+                          float hb, float hd, float c1, float c2, int32_t record_every, float* pos_rec,
+                          float* pot_rec, const float* centers, int32_t natoms, int32_t dim, float scale,
+                          float half_log_det, int32_t has_box, double boxlength, nfk_stream_t stream);
+int nfk_gmix_langevin(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out,
+                      int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out, int64_t batch,
+                      int32_t nsteps, int64_t step0, int64_t row_base, int64_t seed, int32_t zero_mean,
+                      float hb, float hd, float c1, float c2, int32_t record_every, float* pos_rec,
+                      float* pot_rec, const float* centers, const float* scales, const float* hlds,
+                      int32_t npart, int32_t dim, int32_t ncenters, nfk_stream_t stream);
+int nfk_lj_langevin(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out,
+                    int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out, int64_t batch, int32_t nsteps,
+                    int64_t step0, int64_t row_base, int64_t seed, int32_t zero_mean, float hb, float hd,
+                    float c1, float c2, int32_t record_every, float* pos_rec, float* pot_rec, int32_t n,
+                    int32_t dim, double boxlength, double sigma, double epsilon, int32_t has_cutoff,
+                    double cutoff, int32_t shift, nfk_stream_t stream);
+int nfk_eam_langevin(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out,
+                     int64_t ldxo, float* v_out, int64_t ldvo, float* pot_out, int64_t batch, int32_t nsteps,
+                     int64_t step0, int64_t row_base, int64_t seed, int32_t zero_mean, float hb, float hd,
+                     float c1, float c2, int32_t record_every, float* pos_rec, float* pot_rec, int32_t n,
+                     const float* rtab, int32_t nr, double dr, const float* ftab, int32_t nrho, double drho,
+                     double f_end, double fp_end, double lx, double ly, double lz, double rc,
+                     nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Bennett acceptance ratio (applications/src/bar.py:16-68), `problems`
  * independent solves in one launch, and the exponential averages of
  * test.py:67-68.  Problem p works on wf_i = w_f[idx_f ? idx_f[p*ldif + i] : i],

@@ -9,6 +9,8 @@ The applications' priors and targets (applications/src/systems.py):
     from normalizingflow_amd.systems import EinsteinCrystal, GaussianMixture, LJ
 Structure of a batch of configurations (no reference counterpart):
     from normalizingflow_amd.observables import pair_histogram, rdf, coordination
+Counter-based random numbers of the device, restated for the CPU:
+    from normalizingflow_amd.rng import philox4x32, philox_words, philox_normal
 """
 from . import config  # noqa: F401
 from . import systems  # noqa: F401

@@ -253,6 +253,33 @@ SIGNATURES = {
         I32,                            # n
         P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
         F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
+    "nfk_philox_fill": (ctypes.c_int, [
+        P, I32, I64, I32, I32,          # out, normals, rows, n, dim
+        I64, I64, I64, I32, I32, P]),   # step, row_base, seed, tag, zero_mean, stream
+    "nfk_einstein_langevin": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, I64, I64, I64, I32,   # batch, nsteps, step0, row_base, seed, zero_mean
+        F32, F32, F32, F32, I32, P, P,  # hb, hd, c1, c2, record_every, pos_rec, pot_rec
+        P, I32, I32, F32, F32,          # centers, natoms, dim, scale, half_log_det
+        I32, F64, P]),                  # has_box, boxlength, stream
+    "nfk_gmix_langevin": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, I64, I64, I64, I32,   # batch, nsteps, step0, row_base, seed, zero_mean
+        F32, F32, F32, F32, I32, P, P,  # hb, hd, c1, c2, record_every, pos_rec, pot_rec
+        P, P, P, I32, I32, I32, P]),    # centers, scales, hlds, npart, dim, ncenters, stream
+    "nfk_lj_langevin": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, I64, I64, I64, I32,   # batch, nsteps, step0, row_base, seed, zero_mean
+        F32, F32, F32, F32, I32, P, P,  # hb, hd, c1, c2, record_every, pos_rec, pot_rec
+        I32, I32,                       # n, dim
+        F64, F64, F64, I32, F64, I32, P]),  # boxlength, sigma, epsilon, has_cutoff, cutoff, shift, stream
+    "nfk_eam_langevin": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, pot_out
+        I64, I32, I64, I64, I64, I32,   # batch, nsteps, step0, row_base, seed, zero_mean
+        F32, F32, F32, F32, I32, P, P,  # hb, hd, c1, c2, record_every, pos_rec, pot_rec
+        I32,                            # n
+        P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
+        F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
     "nfk_bar_stage_cap": (ctypes.c_int, []),
     "nfk_bar": (ctypes.c_int, [
         P, I64, P, I64,                 # w_f, n_f, w_r, n_r

@@ -33,6 +33,8 @@ restated for the flow path.
 * ``collect_hmc_data`` / ``integrate_out_v`` / ``relaxation_step`` -- the
   dynamics of applications/src/dynamics.py over systems.py's own integrators
   (no LAMMPS), every trajectory of a call in one launch.
+* ``sample_md`` -- target samples by Langevin dynamics at ``dataset.kT``
+  (systems.*.langevin), the role of the reference's LAMMPS trajectories.
 * ``save_checkpoint`` / ``load_checkpoint`` -- the checkpoint dict of
   train.py:39-40 and the loader of setup.py:102-109 (``load_state_dict``
   with ``strict=False``), read with ``torch.load(weights_only=True)``.
@@ -58,7 +60,7 @@ __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flo
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
            "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
            "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff",
-           "fe_diff_no_training", "metropolize", "metropolized_samples", "structure"]
+           "fe_diff_no_training", "metropolize", "metropolized_samples", "structure", "sample_md"]
 
 
 class CfgNode(dict):
@@ -553,6 +555,41 @@ def structure(cfg, model, potential, nsamples, batchsize=500, nbins=100, r_max=N
     _, g_rew = observables_.rdf(x, box, r_max=r_max, nbins=nbins, log_weights=logw)
     _, g_target = observables_.rdf(target, box, r_max=r_max, nbins=nbins)
     return {"r": r, "g_flow": g_flow, "g_reweighted": g_rew, "g_target": g_target, "ess": reweight_.ess(logw)}
+
+
+def sample_md(cfg, potential, nsamples, x0=None, chains=16, burnin=1000, stride=50, dt=0.005, gamma=10.0, seed=0):
+    """Target samples by Langevin dynamics at ``cfg.dataset.kT`` (the role of the
+    reference's LAMMPS runs with ``integrator="langevin"``, systems.py:25-26):
+    ``chains`` independent chains of ``potential.langevin`` from ``x0``
+    ([nparticles, dim] for every chain, or [chains, nparticles, dim]; default:
+    the centres of the Einstein-crystal prior when ``cfg.prior.type`` is
+    "EinsteinCrystal"), ``burnin`` steps, then one frame of every chain each
+    ``stride`` steps until there are ``nsamples``.  Returns
+    [nsamples, nparticles, dim], what ``potential.update_data`` accepts; frames
+    of one time are adjacent.  The run is a function of ``seed`` alone.  The
+    chains are left in ``potential``'s held position and velocity."""
+    d = cfg.dataset
+    nsamples, chains = int(nsamples), max(1, min(int(chains), int(nsamples)))
+    device = getattr(potential, "device", cfg.device)
+    if x0 is None:
+        if cfg.prior.type != "EinsteinCrystal":
+            raise ValueError("sample_md needs x0 unless cfg.prior.type is 'EinsteinCrystal' (whose centres start "
+                             "the chains)")
+        x0 = systems._centers(cfg.prior.centers if cfg.prior.centers is not None else cfg.prior.lattice_dir,
+                              cfg.prior.dim, device)
+    x0 = torch.as_tensor(x0, dtype=torch.float32).to(device)
+    n, dim = x0.shape[-2:]
+    x0 = x0.expand(chains, n, dim).contiguous() if x0.dim() == 2 else x0
+    if x0.shape[0] != chains:
+        raise ValueError("x0 holds %d chains, chains=%d" % (x0.shape[0], chains))
+    per = -(-nsamples // chains)
+    if not isinstance(potential, (systems.LJ, systems.EAM)):
+        x0 = x0.reshape(chains, n * dim)
+    kw = dict(dt=dt, gamma=gamma, kT=d.kT, seed=seed)
+    potential.set_velocity(None)
+    potential.langevin(int(burnin), init_pos=x0, **kw)
+    frames = potential.langevin(per * int(stride), record_every=int(stride), step0=int(burnin), **kw)[2]
+    return frames.reshape(-1, n, dim)[:nsamples]
 
 
 def fe_diff_no_training(cfg, model, potential, nsamples):

@@ -53,8 +53,15 @@ USE_WIDE_RNVP  RealNVP layers whose conditioners are too wide for the fused kern
 USE_AR_SEQINV  the NSF_AR inverse of layers the fused inverse does not take (Polymer's
                2,048 coordinates) through nfk_ar_seqinv (two launches per column
                issued by the library, fp32); off: the per-column host loop.
+LANGEVIN_STEPS_PER_LAUNCH  the most steps one Langevin launch (systems.*.langevin,
+               nfk_langevin.hip) integrates; a longer run is continued by further
+               launches with the absolute step index carried, bit for bit the
+               single launch.  It keeps a launch short on a shared device: sized
+               so that one launch of 500 rows of 54 Fe atoms stays near 100 ms
+               (0.199 ms per step measured).
 """
 STRICT_CHECKS = True
+LANGEVIN_STEPS_PER_LAUNCH = 500
 USE_FUSED = True
 USE_CHAIN = True
 USE_TRAIN_CHAIN = True

@@ -763,6 +763,95 @@ def eam_hmc_run(x_cur, u_cur, naccept, v_draws, r, *, path_len, dt, scheme, beta
            n, *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
 
 
+# device random numbers and Langevin dynamics (nfk_rng.h, nfk_langevin.hip)
+def _i64(v, name):
+    """An int64 argument.  2^63..2^64-1 goes through as its two's complement, a
+    negative number, so that the library refuses it with its own message."""
+    v = int(v)
+    if not -(1 << 63) <= v < (1 << 64):
+        raise ValueError("%s must be in [0, 2^63), got %d" % (name, v))
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def philox_fill(out, *, n, dim, step, seed, row_base=0, tag=0, zero_mean=False, normals=True):
+    """nfk_philox_fill: ``out`` int32 [rows, n, 4] (raw words) or fp32
+    [rows, n, dim] (normals), contiguous."""
+    dev = _require_hip(out)
+    want = (torch.float32, dim) if normals else (torch.int32, 4)
+    if out.dtype != want[0] or out.dim() != 3 or out.shape[1:] != (n, want[1]) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s [rows, %d, %d] tensor, got %s %s"
+                         % (want[0], n, want[1], out.dtype, tuple(out.shape)))
+    _timed("nfk_philox_fill", dev, "nfk_philox_fill", out.data_ptr(), 1 if normals else 0, out.shape[0], int(n),
+           int(dim), _i64(step, "step"), _i64(row_base, "row_base"), _i64(seed, "seed"), int(tag),
+           1 if zero_mean else 0, _stream(dev))
+
+
+def _langevin_args(x_in, v_in, x_out, v_out, pot, width, nsteps, step0, row_base, seed, zero_mean, consts,
+                   record_every, pos_rec, pot_rec):
+    B = x_in.shape[0]
+    mats = []
+    for t, name in ((x_in, "x_in"), (v_in, "v_in"), (x_out, "x_out"), (v_out, "v_out")):
+        if t.dim() != 2 or t.shape != (B, width):
+            raise ValueError("%s must be [%d, %d], got %s" % (name, B, width, tuple(t.shape)))
+        mats.extend(_mat(t, name))
+    nsteps, step0, record_every = int(nsteps), _i64(step0, "step0"), int(record_every)
+    frames = (step0 + nsteps) // record_every - step0 // record_every if record_every > 0 and nsteps >= 0 else 0
+    hb, hd, c1, c2 = (float(c) for c in consts)
+    return (*mats, _vec(pot, B, "pot"), B, nsteps, step0, _i64(row_base, "row_base"), _i64(seed, "seed"),
+            1 if zero_mean else 0, hb, hd, c1, c2, record_every, _vec(pos_rec, frames * B * width, "pos_rec"),
+            _vec(pot_rec, frames * B, "pot_rec"))
+
+
+def einstein_langevin(x_in, v_in, x_out, v_out, pot, centers, *, nsteps, consts, seed, step0=0, row_base=0,
+                      zero_mean=False, record_every=0, pos_rec=None, pot_rec=None, scale, hld, boxlength=None):
+    """nfk_einstein_langevin: ``nsteps`` BAOAB steps of every row in one launch.
+    ``consts`` = (hb, hd, c1, c2); ``pos_rec`` [frames, B, W] and ``pot_rec``
+    [frames, B] (both or neither), frames = (step0 + nsteps) // record_every -
+    step0 // record_every.  ``x_out`` / ``v_out`` may be ``x_in`` / ``v_in``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, centers, pos_rec, pot_rec)
+    natoms, dim = centers.shape
+    has_box, L = _box(boxlength)
+    _timed("nfk_einstein_langevin", dev, "nfk_einstein_langevin",
+           *_langevin_args(x_in, v_in, x_out, v_out, pot, natoms * dim, nsteps, step0, row_base, seed, zero_mean,
+                           consts, record_every, pos_rec, pot_rec),
+           _vec(centers, natoms * dim, "centers"), natoms, dim, float(scale), float(hld), has_box, L,
+           _stream(dev))
+
+
+def gmix_langevin(x_in, v_in, x_out, v_out, pot, centers, scales, hlds, *, nsteps, consts, seed, npart, step0=0,
+                  row_base=0, zero_mean=False, record_every=0, pos_rec=None, pot_rec=None):
+    """nfk_gmix_langevin; arguments as ``einstein_langevin``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, centers, scales, hlds, pos_rec, pot_rec)
+    M, dim = centers.shape
+    _timed("nfk_gmix_langevin", dev, "nfk_gmix_langevin",
+           *_langevin_args(x_in, v_in, x_out, v_out, pot, int(npart) * dim, nsteps, step0, row_base, seed,
+                           zero_mean, consts, record_every, pos_rec, pot_rec),
+           _vec(centers, M * dim, "centers"), _vec(scales, M, "scales"), _vec(hlds, M, "hlds"), int(npart), dim, M,
+           _stream(dev))
+
+
+def lj_langevin(x_in, v_in, x_out, v_out, pot, *, nsteps, consts, seed, n, dim, boxlength, sigma=1.0, epsilon=1.0,
+                cutoff=None, shift=True, step0=0, row_base=0, zero_mean=False, record_every=0, pos_rec=None,
+                pot_rec=None):
+    """nfk_lj_langevin; rows are [n*dim], other arguments as ``einstein_langevin``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, pos_rec, pot_rec)
+    _timed("nfk_lj_langevin", dev, "nfk_lj_langevin",
+           *_langevin_args(x_in, v_in, x_out, v_out, pot, n * dim, nsteps, step0, row_base, seed, zero_mean,
+                           consts, record_every, pos_rec, pot_rec),
+           n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift), _stream(dev))
+
+
+def eam_langevin(x_in, v_in, x_out, v_out, pot, *, nsteps, consts, seed, n, rtab, ftab, dr, drho, f_end, fp_end,
+                 box, rc, step0=0, row_base=0, zero_mean=False, record_every=0, pos_rec=None, pot_rec=None):
+    """nfk_eam_langevin; rows are [n*3], tables and box as ``eam_potential``, other
+    arguments as ``einstein_langevin``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, pot, rtab, ftab, pos_rec, pot_rec)
+    _timed("nfk_eam_langevin", dev, "nfk_eam_langevin",
+           *_langevin_args(x_in, v_in, x_out, v_out, pot, n * 3, nsteps, step0, row_base, seed, zero_mean, consts,
+                           record_every, pos_rec, pot_rec),
+           n, *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
+
+
 def bar_stage_cap():
     """Largest n_f + n_r whose work values nfk_bar keeps in LDS."""
     return int(_lib.load().nfk_bar_stage_cap())

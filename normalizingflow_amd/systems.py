@@ -5,7 +5,8 @@ the reference's constructor signatures and method names.
 fp32 tensors on the HIP device take the kernels of nfk_systems.hip (one launch
 per log_prob / potential, one per backward; no [B, N, N] temporary for LJ)
 and, for ``integration_step``, of nfk_dynamics.hip (a whole batch of
-trajectories in one launch).
+trajectories in one launch); ``langevin`` is the thermostatted counterpart
+(nfk_langevin.hip, the noise generated in the kernel: rng.py).
 Every other input -- CPU tensors, other float dtypes, parameters that require
 grad, shapes the kernels do not take -- runs the plain-torch restatement in
 this module: the same formulas in the input's dtype, differentiable by
@@ -306,6 +307,136 @@ class _Dynamics:
         self.position, self.velocity = x, v
         return x, pot
 
+    # ------------------------------------------------------------------ Langevin (NVT)
+    _zero_momentum_default = False
+
+    def _lv_nd(self, x):
+        """(particles, dim) of a row of x."""
+        return self.nparticles, self.dim
+
+    def _lv_ok(self, x, nd):
+        return True
+
+    def _closing_potential(self, x):
+        """The potential of a Langevin state or frame, [B]."""
+        with torch.no_grad():
+            return self.potential(x).reshape(-1)
+
+    def langevin(self, nsteps, dt=0.005, gamma=10.0, kT=1.0, mass=1.0, seed=0, init_pos=None,
+                 init_velocity=None, record_every=0, zero_momentum=None, step0=0, row_base=0):
+        """``nsteps`` steps of Langevin dynamics at temperature ``kT`` (the
+        reference's ``fix langevin T T 0.1 seed zero yes``: ``gamma`` = 10 is its
+        damping time 0.1) from the held position and velocity (or ``init_pos``
+        / ``init_velocity``), by the BAOAB splitting.  Per step, in the
+        input's dtype and in this order:
+
+            v = v + hb*F;  x = x + hd*v;  v = c1*v + c2*xi;  x = x + hd*v
+            F = force(x);  v = v + hb*F
+
+        with hb = 0.5 dt / mass, hd = 0.5 dt, c1 = exp(-gamma dt), c2 =
+        sqrt(kT / mass (1 - c1^2)) (evaluated in double; rounded to fp32 once
+        for fp32 inputs) and xi the normals of ``rng.philox_normal`` at
+        (``seed``, absolute step ``step0 + k``, particle, row ``row_base + b``).
+        ``zero_momentum`` (default: True for LJ and EAM, False for
+        EinsteinCrystal and GaussianMixture) removes the noise's mean over a
+        row's particles, so the total momentum stays where it is; a missing
+        velocity (``get_velocity() is None``) is drawn as sqrt(kT / mass) times
+        the tag-1 normals of step ``step0``, mean removed likewise.  Positions
+        are not wrapped.
+
+        Returns (position, potential) and holds the final state as
+        ``integration_step`` does; with ``record_every > 0`` also the frames
+        after every step whose absolute index is a multiple of it
+        ([(step0 + nsteps) // record_every - step0 // record_every, B, ...]:
+        ``nsteps // record_every`` from step 0) and their potentials.
+
+        fp32 device tensors at the kernels' shapes run whole chunks of at most
+        ``config.LANGEVIN_STEPS_PER_LAUNCH`` steps per launch (nfk_langevin.hip;
+        no host sync inside a run).  The noise is keyed by the absolute step
+        and F is recomputed from x, so a run equals, bit for bit, the same run
+        cut into chunks, continued with ``step0``, or split over row blocks
+        with ``row_base``.  CPU, fp64, other shapes, ``use_kernels = False``
+        and ``fused_dynamics = False`` run the per-step path, on the device
+        with the bits of the launch."""
+        from . import config, rng
+        if init_pos is not None:
+            self.set_position(init_pos)
+        if init_velocity is not None:
+            self.set_velocity(init_velocity)
+        nsteps, record_every, step0, row_base, seed = (int(nsteps), int(record_every), int(step0), int(row_base),
+                                                       int(seed))
+        if nsteps < 0 or record_every < 0 or step0 < 0:
+            raise ValueError("nsteps, record_every and step0 must be >= 0")
+        if not (dt > 0 and gamma >= 0 and kT >= 0 and mass > 0):
+            raise ValueError("langevin needs dt > 0, gamma >= 0, kT >= 0 and mass > 0")
+        zm = self._zero_momentum_default if zero_momentum is None else bool(zero_momentum)
+        x = self.position
+        n, dim = nd = self._lv_nd(x)
+        rows = x.numel() // (n * dim)
+        c1 = math.exp(-gamma * dt)
+        consts = (0.5 * dt / mass, 0.5 * dt, c1, math.sqrt(kT / mass * (1.0 - c1 * c1)))
+        vscale = math.sqrt(kT / mass)
+        if x.dtype == torch.float32:
+            consts = tuple(float(np.float32(c)) for c in consts)
+            vscale = float(np.float32(vscale))
+        if self.velocity is None:
+            self.velocity = vscale * rng.philox_normal(seed, rows, n, dim, step0, row_base, tag=1, zero_mean=zm,
+                                                       device=x.device, dtype=x.dtype).reshape(x.shape)
+        v = self.velocity.reshape(x.shape)
+        nframes = (step0 + nsteps) // record_every - step0 // record_every if record_every else 0
+        # (EAM's row cap on integration_step does not apply: the launch won at every measured size)
+        if _Dynamics._dyn_fused_ok(self, x, v) and self._lv_ok(x, nd):
+            xr, vr = self._dyn_rows(x).detach(), self._dyn_rows(v).detach()
+            xo = torch.empty_like(xr, memory_format=torch.contiguous_format)
+            vo = torch.empty_like(vr, memory_format=torch.contiguous_format)
+            pot = torch.empty(rows, dtype=torch.float32, device=xr.device)
+            frames = pots = None
+            if record_every:
+                frames = torch.empty(nframes, rows, n * dim, dtype=torch.float32, device=xr.device)
+                pots = torch.empty(nframes, rows, dtype=torch.float32, device=xr.device)
+            cap = max(1, int(config.LANGEVIN_STEPS_PER_LAUNCH))
+            done = f0 = 0
+            while True:
+                m, s0 = min(cap, nsteps - done), step0 + done
+                fm = (s0 + m) // record_every - s0 // record_every if record_every else 0
+                self._langevin_launch(xr, vr, xo, vo, pot, nd, nsteps=m, consts=consts, seed=seed, step0=s0,
+                                      row_base=row_base, zero_mean=zm, record_every=record_every,
+                                      pos_rec=None if frames is None else frames[f0:f0 + fm],
+                                      pot_rec=None if pots is None else pots[f0:f0 + fm])
+                done, f0, xr, vr = done + m, f0 + fm, xo, vo
+                if done >= nsteps:
+                    break
+            x, v = xo.reshape(x.shape), vo.reshape(x.shape)
+            if frames is not None:
+                frames = frames.reshape(nframes, *x.shape)
+        else:
+            x, v = x.detach(), v.detach()
+            hb, hd, c1, c2 = consts
+            F = self._force_detached(x)
+            frames, pots = [], []
+            for k in range(nsteps):
+                xi = rng.philox_normal(seed, rows, n, dim, step0 + k, row_base, tag=0, zero_mean=zm,
+                                       device=x.device, dtype=x.dtype).reshape(x.shape)
+                v = v + hb * F
+                x = x + hd * v
+                v = c1 * v + c2 * xi
+                x = x + hd * v
+                F = self._force_detached(x)
+                v = v + hb * F
+                if record_every and (step0 + k + 1) % record_every == 0:
+                    frames.append(x)
+                    pots.append(self._closing_potential(x))
+            pot = self._closing_potential(x)
+            if record_every:
+                frames = torch.stack(frames) if frames else x.new_empty((0,) + tuple(x.shape))
+                pots = torch.stack(pots) if pots else pot.new_empty((0, rows))
+        self.position, self.velocity = x, v
+        self._last_force, self._replay = None, (x, v, 1, dt, 1)  # last_force: F(position), on the first read
+        pot = self._dyn_pot_shape(pot, x)
+        if record_every:
+            return x, pot, frames, pots
+        return x, pot
+
 
 class _SimData:
     """The trajectory holder of the reference's SimData (systems.py:107-142):
@@ -447,6 +578,25 @@ class EinsteinCrystal(_KernelBacked):
         K_.einstein_trajectory(x, v, xo, vo, pot, self.centers, path_len=path_len, dt=dt, scheme=sch,
                                scale=scale, hld=hld, boxlength=self.boxlength)
 
+    def _lv_ok(self, x, nd):
+        return self.dim <= 4  # a lane takes one of the four normals of its atom's call
+
+    def _langevin_launch(self, x, v, xo, vo, pot, nd, **kw):
+        scale, hld = self._consts()
+        K_.einstein_langevin(x, v, xo, vo, pot, self.centers, scale=scale, hld=hld, boxlength=self.boxlength, **kw)
+
+    def _closing_potential(self, x):
+        # on the device the trajectory kernels' closing potential (a launch of zero
+        # steps), whose row sum runs in their order: nfk_einstein_logprob's float4
+        # form sums in another, and a per-step run is to have the launch's bits
+        if self._kernel_ok(x):
+            xr = self._dyn_rows(x).detach()
+            xo, pot = torch.empty_like(xr, memory_format=torch.contiguous_format), torch.empty(
+                xr.shape[0], dtype=torch.float32, device=xr.device)
+            self._trajectory(xr, xr, xo, torch.empty_like(xo), pot, 0, 0.0, 1)
+            return pot
+        return super()._closing_potential(x)
+
     def _hmc_ok(self, x_cur, shape):
         return self._kernel_ok(x_cur) and K_.einstein_hmc_supported(self.natoms, self.dim)
 
@@ -578,6 +728,10 @@ class GaussianMixture(_KernelBacked):
         scales, hlds = self._consts()
         K_.gmix_trajectory(x, v, xo, vo, pot, self.centers, scales, hlds, path_len=path_len, dt=dt,
                            scheme=sch, npart=self.nparticles)
+
+    def _langevin_launch(self, x, v, xo, vo, pot, nd, **kw):
+        scales, hlds = self._consts()
+        K_.gmix_langevin(x, v, xo, vo, pot, self.centers, scales, hlds, npart=self.nparticles, **kw)
 
     def _hmc_ok(self, x_cur, shape):
         return self._kernel_ok(x_cur) and K_.gmix_hmc_supported(self.nparticles, self.dim, self.ncenters)
@@ -730,6 +884,19 @@ class LJ(_SimData, _Dynamics):
     def _trajectory(self, x, v, xo, vo, pot, path_len, dt, sch):
         n, dim = self._traj_nd  # the rows are [n*dim]: _integrate notes the split
         K_.lj_trajectory(x, v, xo, vo, pot, path_len=path_len, dt=dt, scheme=sch, n=n, dim=dim, **self._kw())
+
+    _zero_momentum_default = True
+
+    def _lv_nd(self, x):
+        if x.dim() < 2:
+            raise ValueError("LJ positions are [..., n, dim]; got shape %s" % (tuple(x.shape),))
+        return tuple(x.shape[-2:])
+
+    def _lv_ok(self, x, nd):
+        return self.boxlength is not None  # no box: the per-step path raises the reference's TypeError
+
+    def _langevin_launch(self, x, v, xo, vo, pot, nd, **kw):
+        K_.lj_langevin(x, v, xo, vo, pot, n=nd[0], dim=nd[1], **self._kw(), **kw)
 
     def _hmc_ok(self, x_cur, shape):
         # no box: the per-epoch steps raise the reference's TypeError
@@ -979,6 +1146,16 @@ class EAM(_SimData, _Dynamics):
         # the rows are [n*3]: _integrate notes n
         K_.eam_trajectory(x, v, xo, vo, pot, path_len=path_len, dt=dt, scheme=sch, n=self._traj_n,
                           **self._kw(x.device))
+
+    _zero_momentum_default = True
+
+    def _lv_nd(self, x):
+        if x.dim() < 2 or x.shape[-1] != 3:
+            raise ValueError("EAM positions are [..., n, 3]; got shape %s" % (tuple(x.shape),))
+        return tuple(x.shape[-2:])
+
+    def _langevin_launch(self, x, v, xo, vo, pot, nd, **kw):
+        K_.eam_langevin(x, v, xo, vo, pot, n=nd[0], **self._kw(x.device), **kw)
 
     def _hmc_ok(self, x_cur, shape):
         return self.use_kernels and len(shape) >= 2 and shape[-1] == 3 and K_.eam_hmc_supported(shape[-2])
