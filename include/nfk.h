@@ -922,6 +922,50 @@ int nfk_eam_langevin(const float* x_in, int64_t ldxi, const float* v_in, int64_t
                      nfk_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Hamiltonian switching, nfk_switch.hip: `nsteps` BAOAB steps on the mixed
+ * reduced potential u_lam = (1 - lam) u_A + lam U_B / kT between an Einstein
+ * crystal A (u_A = -log p_A; centers [n, dim], scale, half_log_det, has_box,
+ * boxlength_A as nfk_einstein_langevin; natoms_A == n and dim_A == the target's
+ * dim) and the target B of nfk_lj_langevin / nfk_eam_langevin, in ONE launch,
+ * with the switching work accumulated in fp64.  Mapping, LDS arrangement, noise
+ * (tag 0, keyed by seed, absolute step, particle, row), zero_mean, the frame
+ * schedule and the supported shapes are those of the target's *_langevin call.
+ * lam[j], 0 <= j < lam_len, is the schedule indexed by the ABSOLUTE step;
+ * step0 + nsteps < lam_len.  Per step k, l0 = lam[step0+k], l1 = lam[step0+k+1]:
+ *   if (l1 != l0)  w = w + ((double)l1 - (double)l0) * ((double)U_B(x) * inv_kT - (double)u_A(x))
+ *   a = (1.0f - l1) * kT;  b = l1;  F = a * g_A + b * g_B        (fp32, this order)
+ *   v = v + hb*F;  x = x + hd*v;  v = c1*v + c2*xi(step0+k);  x = x + hd*v
+ *   g_A = d log p_A/dx, g_B = -dU_B/dx at the new x;  F = a * g_A + b * g_B;  v = v + hb*F
+ * w starts from work[b] and is written back there (work: fp64 [batch], may be
+ * null), so chunks of a run add in one order.  en_out [batch, 2] receives
+ * (u_A, U_B) at x_out; with record_every > 0 and pos_rec / en_rec (both or
+ * neither) the frames [F, batch, n*dim] and their energies [F, batch, 2].
+ * nsteps == 0 evaluates the energies only (lam may then be null).  U_B has the
+ * bits of nfk_lj_potential / nfk_eam_potential; u_A's row sum runs in the
+ * kernel's own fixed order (nfk_switch.hip's head comment).
+ * NFK_EINVAL, nothing launched: what the target's *_langevin call refuses; a
+ * null or too short schedule with nsteps > 0; natoms_A != n; dim_A != dim;
+ * scale <= 0; NaN kT or inv_kT; exactly one of pos_rec / en_rec.
+ * ------------------------------------------------------------------------- */
+int nfk_lj_switch(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out, int64_t ldxo,
+                  float* v_out, int64_t ldvo, float* en_out, int64_t batch, int32_t nsteps, int64_t step0,
+                  int64_t row_base, int64_t seed, int32_t zero_mean, float hb, float hd, float c1, float c2,
+                  int32_t record_every, float* pos_rec, float* en_rec, int32_t n, int32_t dim, double boxlength,
+                  double sigma, double epsilon, int32_t has_cutoff, double cutoff, int32_t shift,
+                  const float* centers, int32_t natoms_A, int32_t dim_A, float scale, float half_log_det,
+                  int32_t has_box, double boxlength_A, const float* lam, int64_t lam_len, double inv_kT,
+                  float kT, double* work, nfk_stream_t stream);
+int nfk_eam_switch(const float* x_in, int64_t ldxi, const float* v_in, int64_t ldvi, float* x_out, int64_t ldxo,
+                   float* v_out, int64_t ldvo, float* en_out, int64_t batch, int32_t nsteps, int64_t step0,
+                   int64_t row_base, int64_t seed, int32_t zero_mean, float hb, float hd, float c1, float c2,
+                   int32_t record_every, float* pos_rec, float* en_rec, int32_t n, const float* rtab, int32_t nr,
+                   double dr, const float* ftab, int32_t nrho, double drho, double f_end, double fp_end,
+                   double lx, double ly, double lz, double rc, const float* centers, int32_t natoms_A,
+                   int32_t dim_A, float scale, float half_log_det, int32_t has_box, double boxlength_A,
+                   const float* lam, int64_t lam_len, double inv_kT, float kT, double* work,
+                   nfk_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Bennett acceptance ratio (applications/src/bar.py:16-68), `problems`
  * independent solves in one launch, and the exponential averages of
  * test.py:67-68.  Problem p works on wf_i = w_f[idx_f ? idx_f[p*ldif + i] : i],

@@ -280,6 +280,23 @@ SIGNATURES = {
         I32,                            # n
         P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
         F64, F64, F64, F64, F64, F64, P]),  # f_end, fp_end, lx, ly, lz, rc, stream
+    "nfk_lj_switch": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, en_out
+        I64, I32, I64, I64, I64, I32,   # batch, nsteps, step0, row_base, seed, zero_mean
+        F32, F32, F32, F32, I32, P, P,  # hb, hd, c1, c2, record_every, pos_rec, en_rec
+        I32, I32,                       # n, dim
+        F64, F64, F64, I32, F64, I32,   # boxlength, sigma, epsilon, has_cutoff, cutoff, shift
+        P, I32, I32, F32, F32, I32, F64,  # centers, natoms_A, dim_A, scale, half_log_det, has_box, boxlength_A
+        P, I64, F64, F32, P, P]),       # lam, lam_len, inv_kT, kT, work, stream
+    "nfk_eam_switch": (ctypes.c_int, [
+        P, I64, P, I64, P, I64, P, I64, P,  # x_in, ldxi, v_in, ldvi, x_out, ldxo, v_out, ldvo, en_out
+        I64, I32, I64, I64, I64, I32,   # batch, nsteps, step0, row_base, seed, zero_mean
+        F32, F32, F32, F32, I32, P, P,  # hb, hd, c1, c2, record_every, pos_rec, en_rec
+        I32,                            # n
+        P, I32, F64, P, I32, F64,       # rtab, nr, dr, ftab, nrho, drho
+        F64, F64, F64, F64, F64, F64,   # f_end, fp_end, lx, ly, lz, rc
+        P, I32, I32, F32, F32, I32, F64,  # centers, natoms_A, dim_A, scale, half_log_det, has_box, boxlength_A
+        P, I64, F64, F32, P, P]),       # lam, lam_len, inv_kT, kT, work, stream
     "nfk_bar_stage_cap": (ctypes.c_int, []),
     "nfk_bar": (ctypes.c_int, [
         P, I64, P, I64,                 # w_f, n_f, w_r, n_r

@@ -35,6 +35,10 @@ restated for the flow path.
   (no LAMMPS), every trajectory of a call in one launch.
 * ``sample_md`` -- target samples by Langevin dynamics at ``dataset.kT``
   (systems.*.langevin), the role of the reference's LAMMPS trajectories.
+* ``switching_work`` / ``fe_switching`` / ``fe_stratified`` -- the free energy
+  of the target against the (normalised) prior WITHOUT a flow: Hamiltonian
+  switching under Langevin dynamics (systems.Switch) with the work handed to
+  BAR, and constant-lambda strata handed to MBAR; the check of ``fe_diff``.
 * ``save_checkpoint`` / ``load_checkpoint`` -- the checkpoint dict of
   train.py:39-40 and the loader of setup.py:102-109 (``load_state_dict``
   with ``strict=False``), read with ``torch.load(weights_only=True)``.
@@ -60,7 +64,8 @@ __all__ = ["CfgNode", "get_cfg_defaults", "read_input", "tail_bound", "build_flo
            "build_potential", "build_model", "save_checkpoint", "load_checkpoint", "train_step",
            "reverse_kl", "forward_kl", "generate_from_nf", "evaluate", "q_matrix", "collect_hmc_data",
            "integrate_out_v", "relaxation_step", "q_matrix_relaxed", "fe_estimates", "fe_diff",
-           "fe_diff_no_training", "metropolize", "metropolized_samples", "structure", "sample_md"]
+           "fe_diff_no_training", "metropolize", "metropolized_samples", "structure", "sample_md",
+           "switching_work", "fe_switching", "fe_stratified"]
 
 
 class CfgNode(dict):
@@ -590,6 +595,147 @@ def sample_md(cfg, potential, nsamples, x0=None, chains=16, burnin=1000, stride=
     potential.langevin(int(burnin), init_pos=x0, **kw)
     frames = potential.langevin(per * int(stride), record_every=int(stride), step0=int(burnin), **kw)[2]
     return frames.reshape(-1, n, dim)[:nsamples]
+
+
+def _switch_for(cfg, prior, potential):
+    """``systems.Switch(prior, potential, kT)`` after the checks of the switching drivers."""
+    d = cfg.dataset
+    if not hasattr(prior, "log_prob"):
+        raise ValueError("the reference of a switching run must be a normalised density (a prior with log_prob, "
+                         "e.g. EinsteinCrystal); got %s" % type(prior).__name__)
+    width = getattr(prior, "width", None)
+    if width is not None and width != d.nparticles * d.dim:
+        raise ValueError("the reference holds %d coordinates, the config %d particles x %d"
+                         % (width, d.nparticles, d.dim))
+    return systems.Switch(prior, potential, kT=d.kT)
+
+
+def _ramp(schedule, nsteps):
+    """The ramp 0 -> 1 over ``nsteps`` steps as nsteps + 1 fp32 values."""
+    if nsteps < 1:
+        raise ValueError("a switching run needs nsteps >= 1")
+    if isinstance(schedule, str):
+        if schedule != "linear":
+            raise ValueError("schedule must be 'linear' or the nsteps + 1 values of a ramp from 0 to 1")
+        return (torch.arange(nsteps + 1, dtype=torch.float64) / nsteps).float()
+    ramp = torch.as_tensor(schedule, dtype=torch.float32).reshape(-1).cpu()
+    if ramp.numel() != nsteps + 1:
+        raise ValueError("the schedule is too short or too long: %d values for nsteps = %d (needs nsteps + 1)"
+                         % (ramp.numel(), nsteps))
+    return ramp
+
+
+def switching_work(cfg, prior, potential, nsamples, nsteps, direction="forward", equil=0, schedule="linear",
+                   dt=0.005, gamma=10.0, seed=0, x0=None):
+    """The reduced work of ``nsamples`` independent switching trajectories between
+    the normalised ``prior`` (lam = 0) and ``potential`` (lam = 1) at
+    ``cfg.dataset.kT`` (``systems.Switch``), [nsamples] fp64 on the samples'
+    device.  ``direction="forward"``: ``prior.sample(nsamples)``, ``equil`` steps
+    at lam = 0, then lam from 0 to 1 over ``nsteps`` steps.  ``"reverse"``:
+    ``potential.sample(nsamples)`` (or ``x0``), ``equil`` steps at lam = 1, then
+    1 to 0.  ``schedule`` is "linear" or the nsteps + 1 values of a ramp from 0
+    to 1 (walked backwards in reverse).  The signs are those of
+    ``fe_estimates``' ``w_F`` / ``w_R``: with ``nsteps = 1`` the forward work is
+    u_B - u_A at the prior's samples, the reverse work u_A - u_B at the
+    target's.  The run is a function of ``seed`` and the starting samples."""
+    d = cfg.dataset
+    if direction not in ("forward", "reverse"):
+        raise ValueError("direction must be 'forward' or 'reverse', got %r" % (direction,))
+    sw = _switch_for(cfg, prior, potential)
+    nsteps, equil = int(nsteps), int(equil)
+    if equil < 0:
+        raise ValueError("equil must be >= 0")
+    ramp = _ramp(schedule, nsteps)
+    if direction == "forward":
+        x = prior.sample(nsamples)
+        lam = torch.cat((torch.zeros(equil), ramp))
+    else:
+        x = potential.sample(nsamples) if x0 is None else x0
+        lam = torch.cat((torch.ones(equil), ramp.flip(0)))
+    x = _sim_positions(potential, x.detach().reshape(len(x), -1), d.dim)
+    sw.set_velocity(None)
+    return sw.switch(lam, dt=dt, gamma=gamma, seed=seed, init_pos=x)[1]
+
+
+def fe_switching(cfg, prior, potential, nsamples, nsteps, nboot=0, generator=None, **kw):
+    """The free-energy difference per particle between ``prior`` and
+    ``potential`` WITHOUT a flow: ``nsamples`` forward and ``nsamples`` reverse
+    switching trajectories of ``nsteps`` steps (``switching_work``, whose other
+    keyword arguments ``kw`` are; the reverse run takes ``seed + 1``), and their
+    work values through ``bar.bar_solve``.  Returns ``(bar, md, nf)`` in the
+    units and layout of ``fe_estimates`` (its formulas with a zero offset:
+    ``bar = DeltaF / nparticles * kT``, ``nf`` the forward exponential average
+    ``log mean exp(w_F)`` and ``md`` the reverse one ``-log mean exp(w_R)``, scaled
+    alike), and with ``nboot`` > 0 the bootstrap standard deviations ``(bar_err,
+    md_err, nf_err)`` (``bar.bootstrap``), all 0-d fp64 tensors on the samples'
+    device.  With the flow's prior as ``prior`` the result is directly
+    comparable with ``fe_diff(cfg, model, potential, ...)``: both estimate
+    -kT / N ln Z_target, this one from the dynamics alone.  On the device the
+    work values go to the BAR kernel in fp32."""
+    d = cfg.dataset
+    seed, x0 = int(kw.pop("seed", 0)), kw.pop("x0", None)
+    w_F = switching_work(cfg, prior, potential, nsamples, nsteps, direction="forward", seed=seed, **kw)
+    w_R = switching_work(cfg, prior, potential, nsamples, nsteps, direction="reverse", seed=seed + 1, x0=x0, **kw)
+    if w_F.is_cuda:
+        w_F, w_R = w_F.float(), w_R.float()
+
+    def scaled(o):
+        return tuple(sgn * o[..., j] / d.nparticles * d.kT for j, sgn in ((0, 1.0), (2, -1.0), (1, 1.0)))
+
+    est = scaled(bar_.bar_solve(w_F, w_R)[0][0])
+    if not nboot:
+        return est
+    boot = scaled(bar_.bootstrap(w_F, w_R, nboot, generator=generator))
+    return est + tuple(b.std() for b in boot)
+
+
+def fe_stratified(cfg, prior, potential, lambdas, nsamples, equil, stride, chains=16, dt=0.005, gamma=10.0,
+                  seed=0, x0=None):
+    """The same difference by stratification: one constant-lam run of
+    ``systems.Switch`` per value of ``lambdas`` (2 <= K <= 8, the states of the
+    MBAR launch; the first and the last are the end states), ``chains`` chains
+    each, ``equil`` steps and then one recorded (u_A, U_B) pair of every chain
+    each ``stride`` steps until there are ``nsamples`` per state.  State 0 starts
+    from ``prior.sample(chains)`` (or ``x0``), every later state from where the
+    one before it ended; state k runs with ``seed + k``.  The pairs give
+    ``u[n, k] = (1 - lam_k) u_A + lam_k U_B / kT`` of every sample in every state
+    (in fp64, less each sample's minimum over the states, which MBAR does not see),
+    ``mbar.mbar_solve`` gives f, and the result is ``((f_K - f_1) / nparticles *
+    kT, its asymptotic error from mbar.mbar_std)`` as 0-d fp64 tensors.  The error
+    treats the samples as independent: choose ``stride`` past the correlation
+    time."""
+    d = cfg.dataset
+    lams = [float(v) for v in lambdas]
+    if not 2 <= len(lams) <= 8:
+        raise ValueError("fe_stratified takes 2 <= K <= 8 values of lambda, got %d" % len(lams))
+    sw = _switch_for(cfg, prior, potential)
+    nsamples, equil, stride = int(nsamples), int(equil), int(stride)
+    if nsamples < 1 or equil < 0 or stride < 1:
+        raise ValueError("fe_stratified needs nsamples >= 1, equil >= 0 and stride >= 1")
+    chains = max(1, min(int(chains), nsamples))
+    per = -(-nsamples // chains)
+    x = prior.sample(chains) if x0 is None else x0
+    x = _sim_positions(potential, x.detach().reshape(len(x), -1), d.dim)
+    pairs = []
+    for k, lam_k in enumerate(lams):
+        lam = torch.full((equil + per * stride + 1,), lam_k)
+        kw = dict(dt=dt, gamma=gamma, seed=int(seed) + k)
+        sw.set_velocity(None)
+        sw.switch(lam, nsteps=equil, init_pos=x, **kw)
+        out = sw.switch(lam, nsteps=per * stride, record_every=stride, step0=equil, **kw)
+        x = out[0]
+        pairs.append(out[4].reshape(-1, 2)[:nsamples].double())
+    en = torch.cat(pairs)  # the states' blocks in order
+    lam_t = torch.tensor(lams, dtype=torch.float64, device=en.device)
+    u = (1.0 - lam_t) * en[:, :1] + lam_t * (en[:, 1:] / d.kT)
+    u = u - u.amin(dim=1, keepdim=True)
+    if u.is_cuda:
+        u = u.float()
+    n_k = [nsamples] * len(lams)
+    f, _, gram = mbar_.mbar_solve(u, n_k)
+    K = len(lams)
+    return ((f[0, K - 1] - f[0, 0]) / d.nparticles * d.kT,
+            mbar_.mbar_std(gram, n_k, 0, K - 1)[0] / d.nparticles * d.kT)
 
 
 def fe_diff_no_training(cfg, model, potential, nsamples):

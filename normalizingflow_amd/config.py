@@ -58,7 +58,9 @@ LANGEVIN_STEPS_PER_LAUNCH  the most steps one Langevin launch (systems.*.langevi
                launches with the absolute step index carried, bit for bit the
                single launch.  It keeps a launch short on a shared device: sized
                so that one launch of 500 rows of 54 Fe atoms stays near 100 ms
-               (0.199 ms per step measured).
+               (0.199 ms per step measured).  The switching
+               launches (systems.Switch.switch, nfk_switch.hip) are cut by it too:
+               0.295 ms per step at the same shape (section 12.4).
 """
 STRICT_CHECKS = True
 LANGEVIN_STEPS_PER_LAUNCH = 500

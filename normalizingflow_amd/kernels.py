@@ -852,6 +852,60 @@ def eam_langevin(x_in, v_in, x_out, v_out, pot, *, nsteps, consts, seed, n, rtab
            n, *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc), _stream(dev))
 
 
+def _switch_args(x_in, v_in, x_out, v_out, en, width, nsteps, step0, row_base, seed, zero_mean, consts,
+                 record_every, pos_rec, en_rec):
+    """``_langevin_args`` with the energy pairs ``en`` [B, 2] and ``en_rec`` [frames, B, 2]
+    in the places of the potentials."""
+    B = x_in.shape[0]
+    a = _langevin_args(x_in, v_in, x_out, v_out, None, width, nsteps, step0, row_base, seed, zero_mean, consts,
+                       record_every, pos_rec, None)
+    nsteps, step0, rec = a[10], a[11], a[19]
+    frames = (step0 + nsteps) // rec - step0 // rec if rec > 0 and nsteps >= 0 else 0
+    return (*a[:8], _vec(en, 2 * B, "en"), *a[9:21], _vec(en_rec, frames * B * 2, "en_rec"))
+
+
+def _switch_tail(centers, n, dim, scale, hld, boxlength_A, lam, kT, work, B):
+    """The Einstein crystal, the schedule and the work buffer of a switching call."""
+    natoms, dim_a = centers.shape
+    has_box, L = _box(boxlength_A)
+    if lam is not None and (lam.dtype != F32 or lam.dim() != 1 or not lam.is_contiguous()):
+        raise ValueError("lam must be a contiguous float32 vector")
+    return (_vec(centers, natoms * dim_a, "centers"), natoms, dim_a, float(scale), float(hld), has_box, L,
+            _ptr(lam), 0 if lam is None else lam.numel(), 1.0 / float(kT), float(kT),
+            _vec(work, B, "work", torch.float64))
+
+
+def lj_switch(x_in, v_in, x_out, v_out, en, centers, lam, *, nsteps, consts, seed, kT, n, dim, boxlength, scale,
+              hld, boxlength_A=None, sigma=1.0, epsilon=1.0, cutoff=None, shift=True, step0=0, row_base=0,
+              zero_mean=False, record_every=0, pos_rec=None, en_rec=None, work=None):
+    """nfk_lj_switch: ``nsteps`` BAOAB steps on (1 - lam) u_A + lam U_B / kT between the
+    Einstein crystal (``centers`` [n, dim], ``scale``, ``hld``, ``boxlength_A``) and the LJ
+    target in one launch.  ``lam`` fp32 [L] is indexed by the absolute step (``step0 +
+    nsteps < L``; None with ``nsteps = 0``); ``en`` [B, 2] receives (u_A, U_B) at
+    ``x_out``, ``work`` fp64 [B] (or None) is added to in place; ``pos_rec``
+    [frames, B, n*dim] and ``en_rec`` [frames, B, 2] come together.  Other arguments as
+    ``lj_langevin``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, en, centers, lam, pos_rec, en_rec, work)
+    _timed("nfk_lj_switch", dev, "nfk_lj_switch",
+           *_switch_args(x_in, v_in, x_out, v_out, en, n * dim, nsteps, step0, row_base, seed, zero_mean, consts,
+                         record_every, pos_rec, en_rec),
+           n, dim, *_lj_consts(boxlength, sigma, epsilon, cutoff, shift),
+           *_switch_tail(centers, n, dim, scale, hld, boxlength_A, lam, kT, work, x_in.shape[0]), _stream(dev))
+
+
+def eam_switch(x_in, v_in, x_out, v_out, en, centers, lam, *, nsteps, consts, seed, kT, n, rtab, ftab, dr, drho,
+               f_end, fp_end, box, rc, scale, hld, boxlength_A=None, step0=0, row_base=0, zero_mean=False,
+               record_every=0, pos_rec=None, en_rec=None, work=None):
+    """nfk_eam_switch; rows are [n*3], tables and box as ``eam_potential``, other
+    arguments as ``lj_switch``."""
+    dev = _require_hip(x_in, v_in, x_out, v_out, en, centers, lam, rtab, ftab, pos_rec, en_rec, work)
+    _timed("nfk_eam_switch", dev, "nfk_eam_switch",
+           *_switch_args(x_in, v_in, x_out, v_out, en, n * 3, nsteps, step0, row_base, seed, zero_mean, consts,
+                         record_every, pos_rec, en_rec),
+           n, *_eam_consts(rtab, ftab, dr, drho, f_end, fp_end, box, rc),
+           *_switch_tail(centers, n, 3, scale, hld, boxlength_A, lam, kT, work, x_in.shape[0]), _stream(dev))
+
+
 def bar_stage_cap():
     """Largest n_f + n_r whose work values nfk_bar keeps in LDS."""
     return int(_lib.load().nfk_bar_stage_cap())

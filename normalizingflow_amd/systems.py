@@ -22,6 +22,11 @@ training and HIP-graph capture (models._prior_log_prob).
 table file (``read_setfl``) over every periodic image within the cutoff, by
 the kernels of nfk_eam.hip.
 
+``Switch`` integrates Langevin dynamics on the lambda-mixed Hamiltonian
+between a normalised reference (the Einstein crystal) and a target and
+accumulates the switching work (nfk_switch.hip): the free energy without a
+flow, app.fe_switching.
+
 Out of scope: LAMMPS itself and plotting.  HMC is in hmc.py, the BAR estimator
 in bar.py, MBAR in mbar.py.
 """
@@ -36,7 +41,7 @@ from torch.autograd.function import once_differentiable
 from . import kernels as K_
 from .flows import check_status
 
-__all__ = ["EinsteinCrystal", "GaussianMixture", "LJ", "EAM", "read_xyz", "load_position", "read_setfl"]
+__all__ = ["EinsteinCrystal", "GaussianMixture", "LJ", "EAM", "Switch", "read_xyz", "load_position", "read_setfl"]
 
 _LOG_2PI = math.log(2 * math.pi)
 
@@ -1168,3 +1173,254 @@ class EAM(_SimData, _Dynamics):
             raise ValueError("EAM positions are [..., n, 3]; got shape %s" % (tuple(x.shape),))
         self._traj_n = x.shape[-2]
         return super()._integrate(x, v, path_len, dt, sch, keep_force)
+
+
+# ---------------------------------------------------------------------------
+class Switch:
+    """Hamiltonian switching between a normalised reference A and a target B:
+    Langevin dynamics at temperature ``kT`` on the mixed reduced potential
+
+        u_lam(x) = (1 - lam) u_A(x) + lam u_B(x),   u_A = -log p_A,  u_B = U_B / kT
+
+    with the switching work accumulated along the way (Frenkel-Ladd /
+    Jarzynski-Crooks; ``app.fe_switching`` hands it to BAR).  ``reference`` is
+    an ``EinsteinCrystal`` (or any system whose ``potential`` is minus a
+    normalised log density), ``target`` an ``LJ``, an ``EAM`` or any system
+    with ``potential`` and ``get_force``.  Positions have the target's shape
+    ([..., n, dim] for LJ and EAM, [B, W] otherwise).
+
+    ``lam`` is an fp32 schedule indexed by the ABSOLUTE step, ``lam[j]`` for
+    ``0 <= j <= total steps``: linear, any other monotone ramp, or constant.
+    Per step k, with l0 = lam[step0 + k] and l1 = lam[step0 + k + 1]:
+
+        if l1 != l0:  w = w + (double(l1) - double(l0)) * (double(U_B(x)) * (1 / kT) - double(u_A(x)))
+        a = (1 - l1) * kT;  b = l1;  F = a * g_A + b * g_B
+        v = v + hb*F;  x = x + hd*v;  v = c1*v + c2*xi;  x = x + hd*v
+        g_A = reference.get_force(x);  g_B = target.get_force(x);  F = a * g_A + b * g_B;  v = v + hb*F
+
+    i.e. the work first, at the position before the step, then one BAOAB step
+    under l1 with the constants, the noise (tag 0, keyed by seed, absolute step,
+    particle, row) and ``zero_momentum`` of ``langevin`` at ``kT``.
+    ``zero_momentum`` defaults to False here: the Einstein field pins the centre
+    of mass, so its forces do not sum to zero.  Centre-of-mass and finite-size
+    corrections of the Einstein-crystal method are out of scope: the work is
+    that of the two Hamiltonians as they are given.
+
+    fp32 device tensors with an ``EinsteinCrystal`` reference and an ``LJ`` or
+    ``EAM`` target at the kernels' shapes take nfk_switch.hip: chunks of at most
+    ``config.LANGEVIN_STEPS_PER_LAUNCH`` steps per launch, no host sync inside a
+    run.  Everything else -- CPU, fp64, ``use_kernels`` or ``fused_dynamics``
+    off, other pairs of systems -- takes the per-step path: torch ops over the
+    two ``get_force`` and the energies, in the input's dtype.  On the device the
+    per-step path has the bits of the launch in x, v, the energies and the work
+    (its energies are the kernel's own zero-step call, whose u_A row sum runs in
+    the kernel's order).  The schedule is read by absolute index, the noise is
+    keyed by the absolute step and the work is added to the carried buffer in
+    step order, so a run equals, bit for bit, the same run cut into chunks
+    (``step0``, ``work``) or split over row blocks (``row_base``)."""
+
+    fused_dynamics = True
+
+    def __init__(self, reference, target, kT=1.0):
+        if not kT > 0:
+            raise ValueError("Switch needs kT > 0")
+        self.reference, self.target, self.kT = reference, target, float(kT)
+        self.position = self.velocity = None
+
+    def set_position(self, position):
+        self.position = position
+
+    def get_position(self):
+        return self.position
+
+    def set_velocity(self, velocity):
+        self.velocity = velocity
+
+    def get_velocity(self):
+        return self.velocity
+
+    # ------------------------------------------------------------------ shapes and routing
+    def _nd(self, x):
+        """(particles, dim) of a row of x; ValueError when A and B disagree."""
+        sysnd = self.target if hasattr(self.target, "_lv_nd") else self.reference
+        n, dim = sysnd._lv_nd(x)
+        wa = getattr(self.reference, "width", None)
+        if wa is not None and wa != n * dim:
+            raise ValueError("the reference holds %d coordinates per configuration, the target %d x %d"
+                             % (wa, n, dim))
+        return n, dim
+
+    @staticmethod
+    def _as(system, x, rows, n, dim):
+        """x in the shape ``system`` takes positions in."""
+        return x.reshape(rows, n, dim) if isinstance(system, (LJ, EAM)) else x.reshape(rows, n * dim)
+
+    def _kernels_ok(self, x, nd):
+        A, B = self.reference, self.target
+        n, dim = nd
+        if not (isinstance(A, EinsteinCrystal) and isinstance(B, (LJ, EAM)) and x.dim() >= 2):
+            return False
+        if not (A.natoms == n and A.dim == dim and A._kernel_ok(x) and B._kernel_ok(x)):
+            return False
+        return B.boxlength is not None
+
+    def _launch_ok(self, x, v, nd):
+        return (self._kernels_ok(x, nd) and self.fused_dynamics and self.reference.fused_dynamics
+                and self.target.fused_dynamics and torch.is_tensor(v) and v.dtype == x.dtype
+                and v.device == x.device)
+
+    def _launch(self, xr, vr, xo, vo, en, lam, nd, **kw):
+        A, B = self.reference, self.target
+        scale, hld = A._consts()
+        kw = dict(kw, kT=self.kT, scale=scale, hld=hld, boxlength_A=A.boxlength)
+        if isinstance(B, LJ):
+            K_.lj_switch(xr, vr, xo, vo, en, A.centers, lam, n=nd[0], dim=nd[1], **B._kw(), **kw)
+        else:
+            K_.eam_switch(xr, vr, xo, vo, en, A.centers, lam, n=nd[0], **B._kw(xr.device), **kw)
+
+    # ------------------------------------------------------------------ energies
+    def energies(self, x):
+        """(u_A [B], U_B [B]) of the configurations x."""
+        x = x.detach()
+        n, dim = nd = self._nd(x)
+        rows = x.numel() // (n * dim)
+        if self._kernels_ok(x, nd):
+            xr = self.target._dyn_rows(x)
+            en = torch.empty(rows, 2, dtype=torch.float32, device=x.device)
+            self._launch(xr, xr, torch.empty_like(xr, memory_format=torch.contiguous_format),
+                         torch.empty_like(xr, memory_format=torch.contiguous_format), en, None, nd, nsteps=0,
+                         consts=(0.0, 0.0, 0.0, 0.0), seed=0)
+            return en[:, 0], en[:, 1]
+        with torch.no_grad():
+            return (self.reference.potential(self._as(self.reference, x, rows, n, dim)).reshape(-1),
+                    self.target.potential(self._as(self.target, x, rows, n, dim)).reshape(-1))
+
+    def potential(self, x, lam):
+        """u_lam(x) = (1 - lam) u_A + lam U_B / kT, [B]."""
+        ua, ub = self.energies(x)
+        return (1.0 - lam) * ua + lam * (ub / self.kT)
+
+    def _forces(self, x, rows, n, dim):
+        out = []
+        for system in (self.reference, self.target):
+            xs = self._as(system, x, rows, n, dim)
+            if hasattr(system, "_force_detached"):
+                g = system._force_detached(xs)
+            else:
+                with torch.enable_grad():
+                    g = system.get_force(xs.detach()).detach()
+            out.append(g.reshape(x.shape))
+        return out
+
+    # ------------------------------------------------------------------ the run
+    def switch(self, lam, nsteps=None, dt=0.005, gamma=10.0, mass=1.0, seed=0, init_pos=None, init_velocity=None,
+               record_every=0, zero_momentum=False, step0=0, row_base=0, work=None):
+        """``nsteps`` switching steps (default: to the end of ``lam``) from the
+        held position and velocity (or ``init_pos`` / ``init_velocity``; a
+        missing velocity is drawn as ``langevin`` draws it: sqrt(kT / mass)
+        times the tag-1 normals of step ``step0``).  ``work`` (fp64 [B], default
+        zeros) is the work carried in; it is not modified.
+
+        Returns (position, work [B] fp64, energies [B, 2] = (u_A, U_B) at the
+        final position) and holds the final state; with ``record_every > 0``
+        also the frames on ``langevin``'s schedule and their energies
+        [F, B, 2].  ``nsteps = 0`` is the energy evaluation."""
+        from . import config, rng
+        if init_pos is not None:
+            self.set_position(init_pos)
+        if init_velocity is not None:
+            self.set_velocity(init_velocity)
+        x = self.position
+        lam_t = torch.as_tensor(lam).detach().reshape(-1).to(torch.float32)
+        step0, row_base, seed, record_every = int(step0), int(row_base), int(seed), int(record_every)
+        nsteps = lam_t.numel() - 1 - step0 if nsteps is None else int(nsteps)
+        if nsteps < 0 or record_every < 0 or step0 < 0:
+            raise ValueError("nsteps, record_every and step0 must be >= 0 (and lam must reach step0)")
+        if nsteps > 0 and step0 + nsteps >= lam_t.numel():
+            raise ValueError("the schedule is too short: lam holds %d values, step0 + nsteps = %d needs %d"
+                             % (lam_t.numel(), step0 + nsteps, step0 + nsteps + 1))
+        if not (dt > 0 and gamma >= 0 and mass > 0):
+            raise ValueError("switch needs dt > 0, gamma >= 0 and mass > 0")
+        zm, kT = bool(zero_momentum), self.kT
+        n, dim = nd = self._nd(x)
+        rows = x.numel() // (n * dim)
+        c1 = math.exp(-gamma * dt)
+        consts = (0.5 * dt / mass, 0.5 * dt, c1, math.sqrt(kT / mass * (1.0 - c1 * c1)))
+        vscale = math.sqrt(kT / mass)
+        fp32 = x.dtype == torch.float32
+        if fp32:
+            consts = tuple(float(np.float32(c)) for c in consts)
+            vscale = float(np.float32(vscale))
+        if self.velocity is None:
+            self.velocity = vscale * rng.philox_normal(seed, rows, n, dim, step0, row_base, tag=1, zero_mean=zm,
+                                                       device=x.device, dtype=x.dtype).reshape(x.shape)
+        v = self.velocity.reshape(x.shape)
+        if work is None:
+            w = torch.zeros(rows, dtype=torch.float64, device=x.device)
+        else:
+            w = work.detach().to(device=x.device, dtype=torch.float64).reshape(rows).clone()
+        nframes = (step0 + nsteps) // record_every - step0 // record_every if record_every else 0
+        if self._launch_ok(x, v, nd):
+            xr, vr = self.target._dyn_rows(x).detach(), self.target._dyn_rows(v).detach()
+            xo = torch.empty_like(xr, memory_format=torch.contiguous_format)
+            vo = torch.empty_like(vr, memory_format=torch.contiguous_format)
+            en = torch.empty(rows, 2, dtype=torch.float32, device=xr.device)
+            lam_d = lam_t.to(xr.device).contiguous()
+            frames = ens = None
+            if record_every:
+                frames = torch.empty(nframes, rows, n * dim, dtype=torch.float32, device=xr.device)
+                ens = torch.empty(nframes, rows, 2, dtype=torch.float32, device=xr.device)
+            cap = max(1, int(config.LANGEVIN_STEPS_PER_LAUNCH))
+            done = f0 = 0
+            while True:
+                m, s0 = min(cap, nsteps - done), step0 + done
+                fm = (s0 + m) // record_every - s0 // record_every if record_every else 0
+                self._launch(xr, vr, xo, vo, en, lam_d, nd, nsteps=m, consts=consts, seed=seed, step0=s0,
+                             row_base=row_base, zero_mean=zm, record_every=record_every, work=w,
+                             pos_rec=None if frames is None else frames[f0:f0 + fm],
+                             en_rec=None if ens is None else ens[f0:f0 + fm])
+                done, f0, xr, vr = done + m, f0 + fm, xo, vo
+                if done >= nsteps:
+                    break
+            x, v = xo.reshape(x.shape), vo.reshape(x.shape)
+            if frames is not None:
+                frames = frames.reshape(nframes, *x.shape)
+        else:
+            x, v = x.detach(), v.detach()
+            hb, hd, c1, c2 = consts
+            lam_h = lam_t.cpu().numpy()
+            inv_kT = 1.0 / kT
+            gA, gB = self._forces(x, rows, n, dim)
+            cur = None  # the energies of the current x, once they are known
+            frames, ens = [], []
+            for k in range(nsteps):
+                l0, l1 = lam_h[step0 + k], lam_h[step0 + k + 1]
+                if l1 != l0:
+                    cur = self.energies(x) if cur is None else cur
+                    w = w + (float(l1) - float(l0)) * (cur[1].double() * inv_kT - cur[0].double())
+                if fp32:
+                    a, b = float((np.float32(1.0) - l1) * np.float32(kT)), float(l1)
+                else:
+                    a, b = (1.0 - float(l1)) * kT, float(l1)
+                xi = rng.philox_normal(seed, rows, n, dim, step0 + k, row_base, tag=0, zero_mean=zm,
+                                       device=x.device, dtype=x.dtype).reshape(x.shape)
+                v = v + hb * (a * gA + b * gB)
+                x = x + hd * v
+                v = c1 * v + c2 * xi
+                x = x + hd * v
+                gA, gB = self._forces(x, rows, n, dim)
+                v = v + hb * (a * gA + b * gB)
+                cur = None
+                if record_every and (step0 + k + 1) % record_every == 0:
+                    cur = self.energies(x)
+                    frames.append(x)
+                    ens.append(torch.stack(cur, dim=-1))
+            cur = self.energies(x) if cur is None else cur
+            en = torch.stack(cur, dim=-1)
+            if record_every:
+                frames = torch.stack(frames) if frames else x.new_empty((0,) + tuple(x.shape))
+                ens = torch.stack(ens) if ens else en.new_empty((0, rows, 2))
+        self.position, self.velocity = x, v
+        if record_every:
+            return x, w, en, frames, ens
+        return x, w, en
