@@ -18,8 +18,9 @@ def build(force=False):
     import torch
     import torch.utils.cpp_extension as ce
     src = os.path.join(HERE, "csrc", "nfk_host.cpp")
+    deps = [src, os.path.join(HERE, "csrc", "nfk_bin_search.h")]
     out = target()
-    if not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(src):
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(p) for p in deps):
         return out
     inc = ce.include_paths() + [sysconfig.get_paths()["include"]]
     lib = ce.library_paths()[0]

@@ -170,8 +170,12 @@ struct SubCopy {
 };
 
 // LDS of one workgroup: the sub-record slot, the status words and byte maps,
-// each wave's kC2Tiles x [16][D + 1] row tiles, each wave's kC2Tiles bin
-// lookup tables
+// each wave's kC2Tiles bin lookup tables, each wave's kC2Tiles x [16][D + 1]
+// row tiles.  The tables stand before the row tiles because the epilogues
+// read rows k and k + 1 of a K-row table unclamped: row K of a table is row 0
+// of the next one and, after the last table, the first 256 bytes of a row
+// tile (the 8 tiles are 512 (D + 1) bytes) -- LDS of this workgroup either
+// way, read and thrown away.
 // byte maps of the chain: nl layers' input columns + the output map (+ the
 // training form's nl - 1 saved-input maps)
 __host__ __device__ inline int chain2_map_bytes(int nl, int D, bool saved) {
@@ -181,11 +185,15 @@ __host__ __device__ inline int chain2_map_bytes(int nl, int D, bool saved) {
 inline size_t lds_bytes_chain2(const Layout& L, int nl, bool saved = false) {
     const int D = L.n_lo + L.n_up;
     return (size_t)split_slot_blocks(L) * 1024 + (size_t)((4 * nl + chain2_map_bytes(nl, D, saved) + 15) / 16) * 16 +
-           (size_t)kNsfWaves * kC2Tiles * 16 * (D + 1) * sizeof(float) +
-           (size_t)kNsfWaves * kC2Tiles * L.K * 64 * sizeof(int);
+           (size_t)kNsfWaves * kC2Tiles * L.K * 64 * sizeof(int) +
+           (size_t)kNsfWaves * kC2Tiles * 16 * (D + 1) * sizeof(float);
 }
 
-template <int KBH, bool T1, int K, bool INV>
+// FULL: n_up is a multiple of 16 (a property of the model, chosen by
+// launch_chain2), so every coordinate of every chunk exists: the map and x
+// reads of the spline epilogues are plain, there is no padding column, and
+// the four column numbers of phase A stay in registers for epilogue C's store.
+template <int KBH, bool T1, int K, bool INV, bool FULL>
 __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
     using ArgsK = const __attribute__((address_space(4))) FusedArgs;
     ArgsK* A = (ArgsK*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -209,10 +217,11 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
     const bool saved = A->saves != nullptr;
     const uint8_t* const c_sav = cm + (NL + 1) * D;  // training form: saved-input maps
     const int XS = D + 1;
-    float* const xbase =
-        reinterpret_cast<float*>(lds4 + A->slot_blocks * 64 + (4 * NL + chain2_map_bytes(NL, D, saved) + 15) / 16);
+    int* const scr0 =
+        reinterpret_cast<int*>(lds4 + A->slot_blocks * 64 + (4 * NL + chain2_map_bytes(NL, D, saved) + 15) / 16);
+    int* const scr = scr0 + wid * NTL * K * 64;  // this wave's NTL lookup tables
+    float* const xbase = reinterpret_cast<float*>(scr0 + kNsfWaves * NTL * K * 64);
     float* const xt = xbase + wid * NTL * 16 * XS;  // this wave's NTL row tiles
-    int* const scr = reinterpret_cast<int*>(xbase + kNsfWaves * NTL * 16 * XS) + wid * NTL * K * 64;
     const float* pk = A->packs[0];
     int lyr = 0;
     const int offA = INV ? A->blk_w : 0, offB = INV ? 0 : A->blk_w, offC = 2 * A->blk_w;
@@ -408,6 +417,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
         const float l2e3 = kL2E * un3;
         float ldsum[NTL] = {0.0f, 0.0f};
         int jj4[4];
+        int tc4[4];  // (FULL) the four columns of this lane, phase A to epilogue C's store
         float xv[NTL][4];
         int kb[NTL][4];
         float cw_k[NTL][4], w_k[NTL][4], ch_k[NTL][4], h_k[NTL][4];
@@ -419,8 +429,7 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                 // map reads and x reads unconditional (a guarded read became a
                 // branch with its own LDS round trip per coordinate)
                 // (uniform) n_up a multiple of 16: every chunk's coordinates exist
-                const bool full_up = (A->n_up & 15) == 0;
-                int tc4[4];
+                const bool full_up = FULL || (A->n_up & 15) == 0;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     jj4[r] = jbase + 4 * q + r;
@@ -434,8 +443,8 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                         const float v = xt[(16 * s + sl) * XS + tc4[r]];
                         xv[s][r] = (full_up || jj4[r] < A->n_up) ? v : 0.0f;
                     }
-                    knot_phase<K, true, 0, 4>(acc[s], xv[s], c, l2e3, kb[s], INV ? ch_k[s] : cw_k[s],
-                                                   INV ? h_k[s] : w_k[s], scr + s * K * 64, lane);
+                    knot_phase<K, true, 0, 4, true>(acc[s], xv[s], c, l2e3, kb[s], INV ? ch_k[s] : cw_k[s],
+                                                    INV ? h_k[s] : w_k[s], scr + s * K * 64, lane);
                 }
             }
             epi_end();
@@ -444,8 +453,8 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                 gemm_rec(RecB{}, acc);
 #pragma unroll
                 for (int s = 0; s < NTL; ++s)
-                    knot_phase<K, false, 0, 4>(acc[s], xv[s], c, l2e3, kb[s], INV ? cw_k[s] : ch_k[s],
-                                                    INV ? w_k[s] : h_k[s], scr + s * K * 64, lane);
+                    knot_phase<K, false, 0, 4, true>(acc[s], xv[s], c, l2e3, kb[s], INV ? cw_k[s] : ch_k[s],
+                                                     INV ? w_k[s] : h_k[s], scr + s * K * 64, lane);
             }
             epi_end();
             {
@@ -456,13 +465,16 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                     float* fs = reinterpret_cast<float*>(scr + s * K * 64);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        // epilogue C of k_fused_nsf, op for op
+                        // epilogue C of k_fused_nsf, op for op, but for the table:
+                        // logit j at row j + 1, rows k and k + 1 read unclamped.
+                        // Row 0 (k = 0) and row K (k = K - 1: past the table,
+                        // see lds_bytes_chain2) are never written here; what they
+                        // hold meets only the d_edge selects below.
                         const int k = kb[s][r];
-                        float raw_k = accd[s][0][r], raw_k1 = accd[s][0][r];
 #pragma unroll
-                        for (int j = 0; j < K - 1; ++j) fs[j * 64 + lane] = accd[s][j][r];
-                        raw_k = fs[(k > 0 ? k - 1 : 0) * 64 + lane];
-                        raw_k1 = fs[(k < K - 1 ? k : K - 2) * 64 + lane];
+                        for (int j = 0; j < K - 1; ++j) fs[(j + 1) * 64 + lane] = accd[s][j][r];
+                        const float raw_k = fs[k * 64 + lane];
+                        const float raw_k1 = fs[(k + 1) * 64 + lane];
                         const float dv_k = nfk_deriv_lean_s(raw_k, l2e3, c.min_d);
                         const float dv_k1 = nfk_deriv_lean_s(raw_k1, l2e3, c.min_d);
                         const float d_k = (k == 0) ? c.d_edge : dv_k;
@@ -498,12 +510,17 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
                         float lad = (__builtin_amdgcn_logf(dnum) - 2.0f * __builtin_amdgcn_logf(den)) * kLN2;
                         lad = INV ? -lad : lad;
                         const bool inside = (x >= c.lo) && (x <= c.hi);
-                        const bool live = jj4[r] < A->n_up && row_ok[s];
+                        const bool live = (FULL || jj4[r] < A->n_up) && row_ok[s];
                         out = inside ? out : x;
-                        // past n_up: the padding column (the map re-read: the
-                        // columns held in registers across the epilogues spilled)
-                        const bool okc = jj4[r] < A->n_up;
-                        const int tcol = okc ? (int)c_up[okc ? jj4[r] : 0] : D;
+                        int tcol;
+                        if constexpr (FULL) {
+                            tcol = tc4[r];
+                        } else {
+                            // past n_up: the padding column (the map re-read: the
+                            // columns held in registers across the epilogues spilled)
+                            const bool okc = jj4[r] < A->n_up;
+                            tcol = okc ? (int)c_up[okc ? jj4[r] : 0] : D;
+                        }
                         xt[(16 * s + sl) * XS + tcol] = out;
                         ldsum[s] += (inside && live) ? lad : 0.0f;
                         any_in |= inside && live;
@@ -550,8 +567,11 @@ __global__ __launch_bounds__(64 * kNsfWaves, 2) void k_nsf_chain2(FusedArgs a) {
             }
             m += __shfl_xor(m, 16, 64);
             m += __shfl_xor(m, 32, 64);
-            const float lp = -0.5f * (A->prior_c2pi + m) - A->prior_hld;
-            if (q == 0 && row_ok[s]) A->log_prob[b0 + 16 * s + sl] = lp + ld_acc[s];
+            // (a NaN leaves as the canonical quiet NaN, as from nfk_normal_logprob:
+            // which operand's payload an add of two NaNs keeps is the compiler's choice)
+            float lp = (-0.5f * (A->prior_c2pi + m) - A->prior_hld) + ld_acc[s];
+            lp = lp != lp ? __builtin_nanf("") : lp;
+            if (q == 0 && row_ok[s]) A->log_prob[b0 + 16 * s + sl] = lp;
             if (__any(row_ok[s] && m != m) && lane == 0) atomicOr(cst, NFK_ST_NAN_Z);
         }
     }
@@ -571,14 +591,19 @@ int launch_chain2(const FusedArgs& a, const Layout& L, int K, bool inv, hipStrea
     if (blocks == 0) return 0;
     const size_t lds = lds_bytes_chain2(L, a.nlayers, a.saves != nullptr);
     const dim3 g((unsigned)blocks), b(64 * kNsfWaves);
-#define NFK_C2(h, t, k)                                                                  \
-    if (L.KBH == h && L.T1 == t && K == k) {                                             \
-        if (inv)                                                                         \
-            hipLaunchKernelGGL((k_nsf_chain2<h, t != 0, k, true>), g, b, lds, st, a);    \
-        else                                                                             \
-            hipLaunchKernelGGL((k_nsf_chain2<h, t != 0, k, false>), g, b, lds, st, a);   \
-        hipError_t e = hipGetLastError();                                                \
-        return e == hipSuccess ? 0 : (int)e;                                             \
+    const bool full = a.n_up % 16 == 0;  // every chunk has its 16 coordinates: the FULL instances
+#define NFK_C2(h, t, k)                                                                         \
+    if (L.KBH == h && L.T1 == t && K == k) {                                                    \
+        if (inv && full)                                                                        \
+            hipLaunchKernelGGL((k_nsf_chain2<h, t != 0, k, true, true>), g, b, lds, st, a);     \
+        else if (inv)                                                                           \
+            hipLaunchKernelGGL((k_nsf_chain2<h, t != 0, k, true, false>), g, b, lds, st, a);    \
+        else if (full)                                                                          \
+            hipLaunchKernelGGL((k_nsf_chain2<h, t != 0, k, false, true>), g, b, lds, st, a);    \
+        else                                                                                    \
+            hipLaunchKernelGGL((k_nsf_chain2<h, t != 0, k, false, false>), g, b, lds, st, a);   \
+        hipError_t e = hipGetLastError();                                                       \
+        return e == hipSuccess ? 0 : (int)e;                                                    \
     }
     NFK_CHAIN2_SHAPES(NFK_C2)
 #undef NFK_C2

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/nfk.h"
+#include "nfk_bin_search.h"
 #include "nfk_mfma.h"
 #include "nfk_pack.h"
 #include "nfk_spline.h"
@@ -618,7 +619,13 @@ __device__ __forceinline__ void act_operands(f32x4 (&h)[HT], float c2, h8 (&bh)[
 // Tried: the knot prefixes of coordinate pairs in packed fp32 -- 7 % fewer VALU
 // instructions per layer, yet c3 measured 1 % slower (6.37 vs 6.30 ms per chain,
 // A/B on one box, profiles/r2_c3_flags_ab.txt).
-template <int K, bool SEARCH, int R0 = 0, int R1 = 4>
+// The bin search is nfk_bin_search (nfk_bin_search.h): three compares at K = 8.
+// PAIR: rows kk and kk + 1 without the clamp at the last row (one address, one
+// ds_read2st64).  Row K is never written; what it holds is discarded by the
+// select at kk = K - 1, the only thing it meets.  The caller's LDS layout must
+// own the 256 bytes after the table (k_nsf_chain2 does; the per-layer kernels'
+// tables end their LDS, so they keep the clamp).
+template <int K, bool SEARCH, int R0 = 0, int R1 = 4, bool PAIR = false>
 __device__ __forceinline__ void knot_phase(const f32x4 (&acc)[K], const float (&xv)[4],
                                            const FusedConst& c, float l2e, int (&kb)[4],
                                            float (&ek)[4], float (&sk)[4], int* scr, int lane) {
@@ -647,17 +654,14 @@ __device__ __forceinline__ void knot_phase(const f32x4 (&acc)[K], const float (&
         for (int j = 1; j < K; ++j) t[j] = __builtin_fmaf(t[j], f, (float)j * c.min_bin);
         if (SEARCH) {
             const float xn = __builtin_fmaf(xv[r], c.inv_span, -c.lo * c.inv_span);
-            int k = 0;
-#pragma unroll
-            for (int j = 1; j < K; ++j) k += (xn >= t[j]) ? 1 : 0;
-            kb[r] = k;
+            kb[r] = nfk_bin_search<K>(xn, t);
         }
         const int kk = kb[r];
         // rows 0..K-1 (float bits); t1 is unused when kk = K - 1 (e1 = hi below)
 #pragma unroll
         for (int j = 0; j < K; ++j) scr[j * 64 + lane] = __builtin_bit_cast(int, t[j]);
         const float t0 = __builtin_bit_cast(float, scr[kk * 64 + lane]);
-        const float t1 = __builtin_bit_cast(float, scr[(kk + 1 < K ? kk + 1 : K - 1) * 64 + lane]);
+        const float t1 = __builtin_bit_cast(float, scr[(PAIR || kk + 1 < K ? kk + 1 : K - 1) * 64 + lane]);
         const float e = __builtin_fmaf(c.span, t0, c.lo);
         float e1 = __builtin_fmaf(c.span, t1, c.lo);
         // computed for every lane, then selected: as a conditional the compiler

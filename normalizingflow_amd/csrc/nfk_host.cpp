@@ -14,12 +14,19 @@
 // replacement) and every parameter (storage pointer, version counter); its
 // valid() then compares ~10 K cached words (~20 us at Polymer) instead of
 // re-walking the tree.
+//
+// Also here, because this is the package's host build: bin8(), the two forms of
+// the fused kernels' K = 8 bin search (nfk_bin_search.h) on CPU tensors, so the
+// CPU suite can compare the bisection with the counting form.
+#include <ATen/ATen.h>
 #include <torch/csrc/autograd/python_variable.h>
 #include <torch/csrc/utils/pybind.h>
 
 #include <cstdint>
 #include <memory>
 #include <vector>
+
+#include "nfk_bin_search.h"
 
 namespace {
 
@@ -233,6 +240,26 @@ py::object make_watch(py::list dicts, py::list tensors) {
     return py::cast(w.release(), py::return_value_policy::take_ownership);
 }
 
+// bins of x[i] among the knots t[i][0 .. 7] (float32, CPU, contiguous):
+// form 0 = nfk_bin_count<8>, form 1 = nfk_bin_search8
+at::Tensor bin8(const at::Tensor& t, const at::Tensor& x, int form) {
+    TORCH_CHECK(t.device().is_cpu() && x.device().is_cpu() && t.scalar_type() == at::kFloat &&
+                    x.scalar_type() == at::kFloat && t.dim() == 2 && t.size(1) == 8 && x.dim() == 1 &&
+                    x.size(0) == t.size(0) && t.is_contiguous() && x.is_contiguous(),
+                "bin8: float32 CPU tensors t[N, 8] and x[N], contiguous");
+    TORCH_CHECK(form == 0 || form == 1, "bin8: form 0 (count) or 1 (search)");
+    at::Tensor out = at::empty({x.size(0)}, at::kInt);
+    const float* tp = t.data_ptr<float>();
+    const float* xp = x.data_ptr<float>();
+    int32_t* op = out.data_ptr<int32_t>();
+    for (int64_t i = 0; i < x.size(0); ++i) {
+        float k[8];
+        for (int j = 0; j < 8; ++j) k[j] = tp[8 * i + j];
+        op[i] = form == 0 ? nfk_bin_count<8>(xp[i], k) : nfk_bin_search8(xp[i], k);
+    }
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_nfk_host, m) {
@@ -241,4 +268,5 @@ PYBIND11_MODULE(_nfk_host, m) {
     py::class_<ArWatch>(m, "ArWatch").def("valid", &ArWatch::valid).def("__len__", &ArWatch::size);
     m.def("ar_watch", &ar_watch);
     m.def("make_watch", &make_watch);
+    m.def("bin8", &bin8);
 }

@@ -904,7 +904,7 @@ __global__ __launch_bounds__(256) void k_normal_lp(const float* __restrict__ z, 
         if (ok && c0 == 0) {
             float lp = -0.5f * (c2pi + m) - hld;
             if (logdet) lp = (sign >= 0) ? (lp + logdet[b]) : (lp - logdet[b]);
-            out[b] = lp;
+            out[b] = lp != lp ? __builtin_nanf("") : lp;  // one NaN, whatever the operands' payloads
         }
         // a NaN in the row makes m NaN (squares of infinities stay infinite)
         if (__any(ok && c0 == 0 && m != m) && status != nullptr && (threadIdx.x & 63) == 0)
@@ -913,8 +913,14 @@ __global__ __launch_bounds__(256) void k_normal_lp(const float* __restrict__ z, 
 }
 
 // float4 form for dim % 4 == 0 and 16-B aligned rows: one 16-B load per lane
-// per step; y = z * (1/L) instead of the solve's z / L (<= 1 ulp per element)
-template <int W>
+// per step; y = z * (1/L) instead of the solve's z / L (<= 1 ulp per element).
+// CHAIN (W = 4): the order of the fused chains' prior epilogues (k_fused_nsf,
+// k_nsf_chain2, the RealNVP chain), whose four lanes q of a sample sum the
+// float4 groups q, q + 4, ... and then add as (m0 + m1) + (m2 + m3).
+// group_sum<4> leaves (L0 + L2) + (L1 + L3) in lane 0, so lane c0 takes the
+// groups of q = its two bits swapped.  With it log_prob of a model run as one
+// launch per layer is the chained launch's bit for bit, like z and log|det|.
+template <int W, bool CHAIN = false>
 __global__ __launch_bounds__(256) void k_normal_lp4(const float4* __restrict__ z4, int64_t ldz4,
                                                     const float* __restrict__ logdet, float* out,
                                                     int64_t batch, int dim4, float inv_l, float c2pi,
@@ -924,8 +930,10 @@ __global__ __launch_bounds__(256) void k_normal_lp4(const float4* __restrict__ z
         const int64_t b = r0 + sub;
         const bool ok = b < batch;
         float m = 0.0f;
+        static_assert(!CHAIN || W == 4, "the chains' epilogues sum over four lanes");
+        const int cq = CHAIN ? ((c0 & 1) << 1 | (c0 >> 1)) : c0;
         if (ok)
-            for (int c = c0; c < dim4; c += W) {
+            for (int c = cq; c < dim4; c += W) {
                 const float4 v = z4[b * ldz4 + c];
                 const float y0 = v.x * inv_l, y1 = v.y * inv_l, y2 = v.z * inv_l, y3 = v.w * inv_l;
                 m += (y0 * y0 + y1 * y1) + (y2 * y2 + y3 * y3);
@@ -934,7 +942,7 @@ __global__ __launch_bounds__(256) void k_normal_lp4(const float4* __restrict__ z
         if (ok && c0 == 0) {
             float lp = -0.5f * (c2pi + m) - hld;
             if (logdet) lp = (sign >= 0) ? (lp + logdet[b]) : (lp - logdet[b]);
-            out[b] = lp;
+            out[b] = lp != lp ? __builtin_nanf("") : lp;  // one NaN, whatever the operands' payloads
         }
         // a NaN in the row makes m NaN (squares of infinities stay infinite)
         if (__any(ok && c0 == 0 && m != m) && status != nullptr && (threadIdx.x & 63) == 0)
@@ -953,6 +961,12 @@ extern "C" int nfk_normal_logprob(const float* z, int64_t ldz, const float* logd
     const float lii = scale;
     const float c2pi = (float)(dim * std::log(2.0 * M_PI));
     if (dim % 4 == 0 && ldz % 4 == 0 && ((uintptr_t)z & 15) == 0) {
+        if (dim <= 128) {  // widths a fused chain can hold: its epilogue's order (at most 8 steps per lane)
+            hipLaunchKernelGGL((k_normal_lp4<4, true>), dim3(grid_for_rows(batch, 4)), dim3(256), 0, st,
+                               (const float4*)z, ldz / 4, logdet, out, batch, dim / 4, 1.0f / lii, c2pi,
+                               half_log_det, sign, status);
+            return launch_status("nfk_normal_logprob");
+        }
         const int dim4 = dim / 4, w4 = lanes_for(dim4);
         const unsigned g4 = grid_for_rows(batch, w4);
         const float inv_l = 1.0f / lii;
